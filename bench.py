@@ -6,14 +6,22 @@
   N > 1 : configs[2] — osu_allreduce -d rocm fp32 SUM 256 MiB, one rank per GPU;
           value = busbw = 2(n-1)/n * S / t (max over ranks), plus the 8-byte latency.
 
-Launch: python bench.py [--gpus 1] [--steps K] [--warmup W]
+Launch: python bench.py [--gpus 1] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 A step is one MPI call on resident device buffers (OSU loop: barrier, t0,
-call, t1).  Kernel time comes from HIP events recorded on the library's own
-stream around the kernel launch (mv2h_timing_enable / mv2h_last_kernel_ms),
-in a second loop so the events never sit inside the timed value loop.
-The CPU baseline (rank 0, N = 1 only) times the oracle's restatement of the
-reference op loop on a bounded host sample.
+call, t1).  A plain run sets up, warms up, times the K steps and prints the
+line with the headline value; --dump-outputs DIR also writes what the last
+timed step left in the result buffer (DIR/<name>.npy, fp32; the inputs are
+seeded, so two builds can be compared output for output).
+
+--full adds everything else the line can carry, each in runs of its own after
+the timed steps: the kernel time and roofline (HIP events recorded on the
+library's own stream around the kernel launch, mv2h_timing_enable /
+mv2h_last_kernel_ms, in a second loop so the events never sit inside the timed
+value loop), the other types, ops and collectives, pack / unpack, the 8-byte
+latencies, the OSU sweeps, the RCCL comparator, the validation of every timed
+N > 1 call, and the CPU baseline (rank 0: the oracle's restatement of the
+reference op loop on a bounded host sample).
 """
 import argparse
 import ctypes
@@ -38,6 +46,18 @@ S_BYTES = 256 * 1024 * 1024
 # completion-word events (mv2h_get_info; runtime/coll.cpp wait_done), copied into both lines
 WORD_KEYS = ("done_queried", "done_late", "done_missed", "done_xcd_split")
 WORLD = 0x44000000        # MPI_COMM_WORLD (MPICH ABI)
+DUMP_SAMPLE = 1 << 22     # --dump-outputs: elements written per array (16 MiB of fp32)
+
+
+def dump_output(dirname, name, arr):
+    """--dump-outputs: DIR/<name>.npy in fp32 -- the whole array up to DUMP_SAMPLE elements, of a
+    larger one its first and last element and a fixed seeded sample of those between, in index order."""
+    os.makedirs(dirname, exist_ok=True)
+    if arr.size > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0xD0FF).integers(0, arr.size, DUMP_SAMPLE))
+        idx[0], idx[-1] = 0, arr.size - 1
+        arr = arr[idx]
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def cpu_info():
@@ -148,7 +168,9 @@ def cpu_baseline_nranks_from(h):
                       f"{h['busbw_1MiB_GBps']} GB/s; {h['placement']} of '{h['cpu']}'; {h['what']}"}
 
 
-def reduce_local_run(L, type_name, op_name, nbytes, steps, warmup):
+def reduce_local_run(L, type_name, op_name, nbytes, steps, warmup, kernel_time=True, keep_output=False):
+    """(s per call, kernel s per call or None, count, a slice of the result, the whole result or None)
+    of `steps` timed MPI_Reduce_local calls; the whole result is what the last timed call left."""
     h, desc, size, ext = TYPES[type_name]
     count = nbytes // ext
     a = m.DeviceBuffer(count * ext)
@@ -172,17 +194,21 @@ def reduce_local_run(L, type_name, op_name, nbytes, steps, warmup):
         m.check(L.MPI_Reduce_local(a.ptr, b.ptr, count, h, OPS[op_name]), "MPI_Reduce_local")
     L.mv2h_device_synchronize()
     t = time.perf_counter() - t0
+    out = b.download(dt, count=count) if keep_output else None
     # kernel duration: HIP events around the launch on the library's stream, separate loop
-    L.mv2h_timing_enable(1)
-    kms = []
-    for _ in range(steps):
-        m.check(L.MPI_Reduce_local(a.ptr, b.ptr, count, h, OPS[op_name]), "MPI_Reduce_local")
-        kms.append(L.mv2h_last_kernel_ms())
-    L.mv2h_timing_enable(0)
+    kern_s = None
+    if kernel_time:
+        L.mv2h_timing_enable(1)
+        kms = []
+        for _ in range(steps):
+            m.check(L.MPI_Reduce_local(a.ptr, b.ptr, count, h, OPS[op_name]), "MPI_Reduce_local")
+            kms.append(L.mv2h_last_kernel_ms())
+        L.mv2h_timing_enable(0)
+        kern_s = float(np.mean(kms)) / 1e3
     # spot-check correctness of the last call on a slice (exact single-op fp/int)
     got = b.download(dt, count=4096)
     del a, b
-    return t / steps, float(np.mean(kms)) / 1e3, count, got
+    return t / steps, kern_s, count, got, out
 
 
 def pack_run(L, steps):
@@ -221,13 +247,44 @@ def pack_run(L, steps):
 
 
 def bench_n1(args, L):
-    step_s, kern_s, count, _ = reduce_local_run(L, "MPI_FLOAT", "MPI_SUM", S_BYTES, args.steps, args.warmup)
+    step_s, kern_s, count, _, out = reduce_local_run(L, "MPI_FLOAT", "MPI_SUM", S_BYTES, args.steps, args.warmup,
+                                                     kernel_time=args.full, keep_output=bool(args.dump_outputs))
+    if out is not None:
+        dump_output(args.dump_outputs, "reduce_local_inoutbuf", out)
+        del out
     alg_bytes = 3 * count * 4
     value = alg_bytes / step_s / 1e9
-    achieved = alg_bytes / kern_s / 1e9
     extra = {}
+    line = {
+        "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(step_s * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "configs[1]: MPI_Reduce_local SUM fp32 on 256 MiB device buffers, 1 MI355X",
+                   "count": count, "bytes_per_operand": S_BYTES, "algorithmic_bytes_per_call": alg_bytes,
+                   "api": "MPI_Reduce_local via libmpi.so (MPICH ABI)"},
+        "roofline": None, "cpu_baseline": None, "extra": extra,
+    }
+    if args.full:
+        bench_n1_full(args, L, line, count, alg_bytes / kern_s / 1e9, kern_s)
+    extra["mpi_init_ms"] = {"total": round(m.info("init_us") / 1e3, 1), "hip_start": round(m.info("hip_init_us") / 1e3, 1),
+                            "code_objects": round(m.info("code_load_us") / 1e3, 1),
+                            "what": "MPI_Init wall time on this rank; code objects = loading libmpi.so's gfx950 "
+                                    "code (26 MB, one empty kernel per translation unit)"}
+    # completion-word events of this run (runtime/coll.cpp wait_done): a word still unseen 200 us
+    # after launch, a kernel that ended without raising it, a kernel whose block groups ran on
+    # several XCDs -- a slow call in this line is explained or ruled out by these
+    extra["completion_word"] = {k: m.info(k) for k in WORD_KEYS}
+    if args.full and args.cpu_seconds > 0:
+        extra["cpu_host_allreduce_8rank"] = cpu_baseline_host_allreduce(args.cpu_seconds)
+    return line
+
+
+def bench_n1_full(args, L, line, count, achieved, kern_s):
+    """--full at N = 1: the roofline of the headline kernel, the other (type, op) pairs, host
+    operands, pack / unpack, the 8-byte latency and the CPU baseline, into `line`."""
+    extra = line["extra"]
     for t, op in (("MPI_FLOAT", "MPI_MAX"), ("MPI_INT", "MPI_SUM"), ("MPI_DOUBLE", "MPI_SUM"), ("MPI_DOUBLE", "MPI_MAX")):
-        s, k, c, _ = reduce_local_run(L, t, op, S_BYTES, max(3, args.steps // 2), 2)
+        s, k, c, _, _ = reduce_local_run(L, t, op, S_BYTES, max(3, args.steps // 2), 2)
         extra[f"{t}:{op}"] = {"GB/s_call": round(3 * S_BYTES / s / 1e9, 1), "GB/s_kernel": round(3 * S_BYTES / k / 1e9, 1)}
     # host (pageable) operands: the library stages them to the GPU and back — the
     # PCIe-inclusive rate of the same call (never the headline value)
@@ -284,35 +341,15 @@ def bench_n1(args, L):
             traffic = json.load(open(os.path.join(ROOT, tsrc))).get("hbm_bytes_per_launch")
         except Exception:
             traffic, tsrc = None, None
-    line = {
-        "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(step_s * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "configs[1]: MPI_Reduce_local SUM fp32 on 256 MiB device buffers, 1 MI355X",
-                   "count": count, "bytes_per_operand": S_BYTES, "algorithmic_bytes_per_call": alg_bytes,
-                   "api": "MPI_Reduce_local via libmpi.so (MPICH ABI)"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK, 4), "traffic": traffic, "traffic_source": tsrc,
-                     "kernel": "k_reduce_local<R<SUM,F32>,2>", "kernel_ms": round(kern_s * 1e3, 4)},
-        "cpu_baseline": cpu_baseline_reduce_local(args.cpu_seconds) if args.cpu_seconds > 0 else None,
-        "extra": extra,
-    }
-    extra["mpi_init_ms"] = {"total": round(m.info("init_us") / 1e3, 1), "hip_start": round(m.info("hip_init_us") / 1e3, 1),
-                            "code_objects": round(m.info("code_load_us") / 1e3, 1),
-                            "what": "MPI_Init wall time on this rank; code objects = loading libmpi.so's gfx950 "
-                                    "code (26 MB, one empty kernel per translation unit)"}
-    # completion-word events of this run (runtime/coll.cpp wait_done): a word still unseen 200 us
-    # after launch, a kernel that ended without raising it, a kernel whose block groups ran on
-    # several XCDs -- a slow call in this line is explained or ruled out by these
-    extra["completion_word"] = {k: m.info(k) for k in WORD_KEYS}
-    if args.cpu_seconds > 0:
-        extra["cpu_host_allreduce_8rank"] = cpu_baseline_host_allreduce(args.cpu_seconds)
-    return line
+    line["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK, 4), "traffic": traffic, "traffic_source": tsrc,
+                        "kernel": "k_reduce_local<R<SUM,F32>,2>", "kernel_ms": round(kern_s * 1e3, 4)}
+    line["cpu_baseline"] = cpu_baseline_reduce_local(args.cpu_seconds) if args.cpu_seconds > 0 else None
 
 
-def _timed(L, world, call, steps, warmup, step_call=None):
+def _timed(L, world, call, steps, warmup, step_call=None, kernel_time=True):
     """OSU loop on resident device buffers: warmup, barrier + device sync,
-    `steps` calls, device sync + barrier.  Returns (s per call, mean kernel ms).
+    `steps` calls, device sync + barrier.  Returns (s per call, mean kernel ms or None).
     step_call(i), when given, is the i-th timed call (each timed call its own result buffer, so
     that every one is verified afterwards); the kernel-time loop uses `call`."""
     for _ in range(warmup):
@@ -325,6 +362,8 @@ def _timed(L, world, call, steps, warmup, step_call=None):
     L.mv2h_device_synchronize()
     L.MPI_Barrier(world)
     t = time.perf_counter() - t0
+    if not kernel_time:
+        return t / steps, None
     # kernel durations (HIP events on the library's stream) in a separate loop
     L.mv2h_timing_enable(1)
     kms = []
@@ -603,11 +642,24 @@ def bench_nranks(args, L, rank, size):
     ar = lambda: L.MPI_Allreduce(sb.ptr, rb.ptr, count, F32, SUM, world)  # noqa: E731
     rb.upload(np.zeros(count, dtype=np.float32))
     m.check(ar(), "MPI_Allreduce")
+    rbs = [m.DeviceBuffer(S_BYTES) for _ in range(args.steps)]
+    if not args.full:
+        # a plain run: the timed calls, their time as the maximum over ranks, the last one's result
+        step_s, _ = _timed(L, world, ar, args.steps, args.warmup, kernel_time=False,
+                           step_call=lambda i: L.MPI_Allreduce(sb.ptr, rbs[i].ptr, count, F32, SUM, world))
+        if args.dump_outputs and rank == 0:
+            dump_output(args.dump_outputs, "allreduce_recvbuf", rbs[-1].download(np.float32, count=count))
+        del rbs
+        dm = m.DeviceBuffer.from_array(np.array([step_s], dtype=np.float64))
+        dr = m.DeviceBuffer(8)
+        m.check(L.MPI_Allreduce(dm.ptr, dr.ptr, 1, F64, MAX, world), "max")
+        return plain_nranks_line(size, args.steps, args.warmup, float(dr.download(np.float64)[0]))
     want = _expected_sum(count, size)
     ok = bool(np.array_equal(rb.download(np.float32, count=count), want))
-    rbs = [m.DeviceBuffer(S_BYTES) for _ in range(args.steps)]
     step_s, kms = _timed(L, world, ar, args.steps, args.warmup,
                          step_call=lambda i: L.MPI_Allreduce(sb.ptr, rbs[i].ptr, count, F32, SUM, world))
+    if args.dump_outputs and rank == 0:
+        dump_output(args.dump_outputs, "allreduce_recvbuf", rbs[-1].download(np.float32, count=count))
     verified = sum(bool(np.array_equal(b.download(np.float32, count=count), want)) for b in rbs)
     del rbs
     ok = ok and verified == args.steps and bool(np.array_equal(rb.download(np.float32, count=count), want))
@@ -804,6 +856,21 @@ def pipe_alg_bytes(size):
     return 2.0 * S_BYTES * (1.0 + 2.0 * (size - 1) / size)
 
 
+def plain_nranks_line(size, steps, warmup, step_s):
+    """The N > 1 line of a run without --full: the headline busbw from the timed calls alone
+    (pure, like assemble_nranks_line; `step_s` is the maximum over ranks)."""
+    return {
+        "metric": METRIC, "value": round(2.0 * (size - 1) / size * S_BYTES / step_s / 1e9, 2), "unit": "GB/s",
+        "n_gpus": size, "steps": steps, "warmup": warmup, "ms_per_step": round(step_s * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "configs[2]: osu_allreduce -d rocm fp32 SUM 256 MiB, 1 rank per GPU over xGMI",
+                   "count": S_BYTES // 4, "bytes": S_BYTES,
+                   "algorithm": "pipelined direct RS+AG (pushes into peer arenas over xGMI)",
+                   "validation": "none in this run: --full checks every timed call's whole result"},
+        "roofline": None, "cpu_baseline": None, "extra": {},
+    }
+
+
 def assemble_nranks_line(size, nshare, steps, warmup, t, lat_avg, uop_lines, nrec, p2p_bytes, tiling, traffic, rccl,
                          cpu_baseline=None, checks=None):
     """The N > 1 bench line from max-over-ranks measurements (pure: no GPU, no library calls, so the
@@ -891,10 +958,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--lat-iters", type=int, default=1000)
-    ap.add_argument("--rccl", type=int, default=1, help="N > 1: also time RCCL all_reduce as a comparator")
-    ap.add_argument("--sweep", type=int, default=1, help="N > 1: OSU sweeps of configs[2] / [3] (tools/osu/osu_coll)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result buffer of the last timed step to DIR/<name>.npy (fp32; above "
+                         f"{DUMP_SAMPLE} elements a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else the line can carry "
+                         "(kernel time and roofline, other types / ops / collectives, latencies, sweeps, the RCCL "
+                         "comparator, validation of the timed calls, CPU baselines)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: length of the CPU baselines (0: none)")
+    ap.add_argument("--lat-iters", type=int, default=1000, help="--full: calls of the 8-byte latency loops")
+    ap.add_argument("--rccl", type=int, default=1, help="--full, N > 1: also time RCCL all_reduce as a comparator")
+    ap.add_argument("--sweep", type=int, default=1,
+                    help="--full, N > 1: OSU sweeps of configs[2] / [3] (tools/osu/osu_coll)")
     ap.add_argument("--rccl-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.rccl_child:
@@ -911,7 +986,7 @@ def main():
     else:
         line = bench_nranks(args, L, rank, size)
     L.MPI_Finalize()
-    if rank == 0 and size > 1 and args.cpu_seconds > 0:
+    if rank == 0 and size > 1 and args.full and args.cpu_seconds > 0:
         # configs[0], the reference's host-buffer shared-memory MPI_Allreduce with 8 ranks on this
         # box's cores, in the same run (north_star): rank 0 after MPI_Finalize, when the GPU ranks
         # have stopped spinning on the host, as a fresh child process with a time limit

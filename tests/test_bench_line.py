@@ -55,6 +55,36 @@ def test_one_rank_per_gpu_roofline(n):
     json.dumps(line)  # the line must serialise
 
 
+@pytest.mark.parametrize("n", [2, 8])
+def test_plain_line_has_the_headline_and_nothing_measured_elsewhere(n):
+    """A run without --full: the same value and ms_per_step as the full line for the same step time,
+    none of the figures that take runs of their own."""
+    plain = bench.plain_nranks_line(n, 20, 5, 1e-3)
+    full = bench.assemble_nranks_line(n, 1, 20, 5, _t(), 9e-6, [], 1 << 24, 128 << 20, TILING, (None, None, "n"), None)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "scaling"):
+        assert plain[k] == full[k], k
+    assert plain["ms_per_step"] == 1.0 and plain["roofline"] is None and plain["cpu_baseline"] is None
+    assert plain["extra"] == {}
+    json.dumps(plain)
+
+
+def test_dump_output_is_float32_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: a small array whole; of a large one the ends and a fixed seeded sample, the
+    same indices in every run, so that two builds' files compare element for element."""
+    import numpy as np
+    small = np.arange(1000, dtype=np.float64)
+    bench.dump_output(str(tmp_path / "a"), "small", small)
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    big = np.arange(bench.DUMP_SAMPLE + 12345, dtype=np.float32)
+    bench.dump_output(str(tmp_path / "a"), "big", big)
+    bench.dump_output(str(tmp_path / "b"), "big", big)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.size == bench.DUMP_SAMPLE and a.nbytes <= 64 << 20
+    assert np.array_equal(a, b) and a[0] == 0 and a[-1] == big.size - 1 and np.all(np.diff(a) >= 0)
+    assert len(np.unique(a)) > bench.DUMP_SAMPLE // 2  # spread over the array, not one corner of it
+
+
 CHECKS = {"timed_calls_verified": 20, "timed_calls": 20,
           "completion_word_sum_over_ranks": {"done_queried": 3, "done_late": 0, "done_missed": 0, "done_xcd_split": 0},
           "release_protocol": "light",
