@@ -17,6 +17,8 @@
  *                       -> index_tuned_intra_MV2      allreduce_osu.c:3015-3420
  *   mv2h_reduce         MPIR_Reduce_MV2               src/mpi/coll/reduce_osu.c:2709
  *   mv2h_reduce_scatter MPIR_Reduce_scatter_MV2       src/mpi/coll/red_scat_osu.c:1771
+ *   mv2h_scan           MPIR_Scan_MV2                 src/mpi/coll/scan_osu.c:36 -> scan.c:225
+ *   mv2h_exscan         MPIR_Exscan_MV2               src/mpi/coll/exscan_osu.c -> exscan.c:95
  *   mv2h_allgather      MPIR_Allgather_MV2            src/mpi/coll/allgather_osu.c:2593
  *   mv2h_bcast          MPIR_Bcast_MV2                src/mpi/coll/bcast_osu.c:3347
  *   mv2h_pack_strided   MPID_Segment_pack_device      src/mpid/ch3/channels/mrail/src/gen2/ibv_cuda_util.c:623
@@ -70,6 +72,12 @@ int mv2h_reduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, int
                 void *stream);
 int mv2h_reduce_scatter(const void *sendbuf, void *recvbuf, const size_t *recvcounts, int dtype,
                         int op, void *stream);
+/* MPI_Scan / MPI_Exscan on one node (MPIR_Scan_generic scan.c:73-213, MPIR_Exscan exscan.c:95-220;
+ * on device buffers the reference stages them through the host, scan_osu.c:36-99).  sendbuf ==
+ * (void *)-1 (MPI_IN_PLACE): the operand is read from recvbuf.  Exscan never writes rank 0's
+ * recvbuf.  A job over several nodes is refused with MPI_ERR_OTHER's class before any device work. */
+int mv2h_scan(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);
+int mv2h_exscan(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);
 int mv2h_allgather(const void *sendbuf, void *recvbuf, size_t bytes_per_rank, void *stream);
 int mv2h_bcast(void *buffer, size_t bytes, int root, void *stream);
 int mv2h_barrier(void);
@@ -168,12 +176,17 @@ enum mv2h_coll {
     MV2H_COLL_REDUCE = 1,         /* count; root */
     MV2H_COLL_REDUCE_SCATTER = 2, /* counts[n] */
     MV2H_COLL_ALLREDUCE_RS = 3,   /* pt2pt_rs forced (ring wrapper remainder / IN_PLACE body) */
+    MV2H_COLL_SCAN = 4,           /* MPI_Scan: rank's own program (scan.c:73-213) */
+    MV2H_COLL_EXSCAN = 5,         /* MPI_Exscan: rank's own program; rank 0: res = 0xff, no result (exscan.c:95-220) */
+    MV2H_COLL_SCAN_ALL = 6,       /* MPI_Scan: p[r] = rank r's program, nprog = n (the pipelined kernel's table) */
+    MV2H_COLL_EXSCAN_ALL = 7,     /* MPI_Exscan: the same; p[0].res = 0xff */
 };
 /* opkind: 0 builtin, 1 commutative user op, 2 non-commutative user op.
  * *algo: 0 none, 1 shmem_linear, 2 pt2pt_rs, 3 pt2pt_rd, 4 ring_wrapper,
  * 5 topo_tree, 6 two_level_p2p, 7 binomial, 8 knomial, 9 redscat_gather,
  * 10 rs_ring, 11 rs_rec_halving, 12 rs_pairwise, 13 rs_basic, 14 reduce_topo,
- * 15 rs_noncomm_pof2, 16 rs_noncomm_rd (non-commutative user ops' reduce-scatter).
+ * 15 rs_noncomm_pof2, 16 rs_noncomm_rd (non-commutative user ops' reduce-scatter),
+ * 17 scan_rd, 18 exscan_rd (MPI_Scan / MPI_Exscan: recursive doubling, one result per rank).
  * *unpinned = 1 when the reference's own result depends on message arrival. */
 int mv2h_plan(int coll, int n, int rank, int root, size_t count, const size_t *counts, int dtype, int opkind,
               int in_place, int *algo, int *inner, int *unpinned, mv2h_progset *ps);

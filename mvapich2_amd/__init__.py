@@ -51,6 +51,8 @@ def lib():
         "mv2h_reduce_local": ([c_vp, c_vp, c_sz, c_int, c_int, c_vp], c_int),
         "mv2h_reduce_n": ([ctypes.POINTER(c_vp), c_int, c_vp, c_sz, c_int, c_int, c_int, c_int, c_vp], c_int),
         "mv2h_allreduce": ([c_vp, c_vp, c_sz, c_int, c_int, c_vp], c_int),
+        "mv2h_scan": ([c_vp, c_vp, c_sz, c_int, c_int, c_vp], c_int),
+        "mv2h_exscan": ([c_vp, c_vp, c_sz, c_int, c_int, c_vp], c_int),
         "mv2h_reduce": ([c_vp, c_vp, c_sz, c_int, c_int, c_int, c_vp], c_int),
         "mv2h_reduce_scatter": ([c_vp, c_vp, ctypes.POINTER(c_sz), c_int, c_int, c_vp], c_int),
         "mv2h_allgather": ([c_vp, c_vp, c_sz, c_vp], c_int),
@@ -93,6 +95,10 @@ def lib():
         "MPI_Reduce": ([c_vp, c_vp, c_int, c_int, c_int, c_int, c_int], c_int),
         "MPI_Reduce_scatter": ([c_vp, c_vp, ctypes.POINTER(c_int), c_int, c_int, c_int], c_int),
         "MPI_Reduce_scatter_block": ([c_vp, c_vp, c_int, c_int, c_int, c_int], c_int),
+        "MPI_Scan": ([c_vp, c_vp, c_int, c_int, c_int, c_int], c_int),
+        "MPI_Exscan": ([c_vp, c_vp, c_int, c_int, c_int, c_int], c_int),
+        "MPI_Iscan": ([c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
+        "MPI_Iexscan": ([c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Allgather": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int], c_int),
         "MPI_Bcast": ([c_vp, c_int, c_int, c_int, c_int], c_int),
         "MPI_Op_create": ([c_vp, c_int, ctypes.POINTER(c_int)], c_int),
@@ -224,7 +230,10 @@ class ProgSet(ctypes.Structure):
     _fields_ = [("nprog", ctypes.c_int32), ("pad", ctypes.c_int32), ("blk", ctypes.c_uint64), ("p", Prog * 8)]
 
 
-COLL = {"allreduce": 0, "reduce": 1, "reduce_scatter": 2, "allreduce_rs": 3}
+# "scan" / "exscan": the rank's own program (exscan's rank 0: res = 0xff, no result);
+# "scan_all" / "exscan_all": programs[r] = rank r's (the pipelined kernel's table)
+COLL = {"allreduce": 0, "reduce": 1, "reduce_scatter": 2, "allreduce_rs": 3, "scan": 4, "exscan": 5, "scan_all": 6,
+        "exscan_all": 7}
 
 
 def plan(coll, n, rank, dtype_handle, count=0, counts=None, root=0, opkind=0, in_place=False):

@@ -43,6 +43,12 @@ struct OneShotArgs {
     int *err;
     uint64_t timeout;
     int light;    // 1: signal without the L2 writeback (peers read only uncached arena data)
+    // scan (MPI_Scan / MPI_Exscan, k_oneshot_scan): 1 = this rank evaluates tp.ps.p[0] over its
+    // own operand and the slots of the ranks below it, and pushes its operand only to the ranks
+    // above it; 2 = the same push, no result (MPI_Exscan's rank 0: recv is never written).  The
+    // flags go to and are awaited from every peer, as in every one-shot call (arena-half reuse).
+    // (it sits in the padding behind `light`: every other member keeps its offset)
+    int scan;
     Done done;
     // graph lane (HIP graph capture): epoch and arena half come from the device sequence
     // block at run time (arena_peer / arena_own then point at half 0; `half` = bytes per half)
@@ -71,6 +77,7 @@ enum PipeMode : int {
     PIPE_RED = 2,  // reduce to root: scatter -> reduce -> push to root -> root gathers
     PIPE_AG = 3,   // allgather: push own contribution -> gather
     PIPE_BC = 4,   // broadcast: root scatters segments -> owners push -> gather
+    PIPE_SCAN = 5, // scan / exscan: scatter -> owner computes every rank's value + push -> gather
 };
 
 // Arena layout per rank and region (RS region, AG region):

@@ -393,6 +393,78 @@ __global__ __launch_bounds__(kThreads) void k_oneshot(OneShotArgs a) {
     block_done(a.done);
 }
 
+// One-shot scan (MPI_Scan / MPI_Exscan, small messages): k_oneshot's two phases with this rank's
+// own program a.tp.ps.p[0].  My operand goes to the ranks above me only, and my result reads the
+// slots of the ranks below me only; the flags still go to, and are awaited from, every peer, so
+// that no rank reaches call i + 2 while a peer reads call i's arena half.  a.scan == 2
+// (MPI_Exscan's rank 0): the same push and flags, no result, recv untouched.  A kernel of its own,
+// so that the allreduce's one-shot kernels keep their code and registers.
+template <class Rd, bool SMALL = false>
+__global__ __launch_bounds__(kThreads) void k_oneshot_scan(OneShotArgs a) {
+    using T = typename Rd::T;
+    constexpr int N = 16 / sizeof(T);
+    uint64_t epoch = a.epoch;
+    size_t poff = 0;
+    if (a.dseq) {
+        const SeqBase q = dseq_read(a.dseq);
+        epoch = q.epoch + 1;
+        poff = (q.os & 1) * a.half;
+    }
+    const int blk = blockIdx.x, G = gridDim.x;
+    const int me = a.me;
+    const size_t nvec = SMALL ? 0 : a.nvec;
+    const size_t per = (nvec + G - 1) / G;
+    const size_t vb = (size_t)blk * per;
+    const size_t ve = vb + per < nvec ? vb + per : nvec;
+    const v4u *send = (const v4u *)a.send;
+    // phase A: push my data to slot (me) of every rank above me
+    if constexpr (!SMALL)
+    for (size_t i = vb + threadIdx.x; i < ve; i += kThreads) {
+        const v4u x = send[i];
+#pragma unroll
+        for (int j = 1; j < kMaxRanks; ++j)
+            if (j > me && j < a.n) ((v4u *)(a.arena_peer.p[j] + poff + (size_t)me * a.slot_bytes))[i] = x;
+    }
+    const size_t tail0 = nvec * N;
+    if (blk == 0) {
+        for (size_t e = tail0 + threadIdx.x; e < a.count; e += kThreads) {
+            const T x = ((const T *)a.send)[e];
+#pragma unroll
+            for (int j = 1; j < kMaxRanks; ++j)
+                if (j > me && j < a.n) ((T *)(a.arena_peer.p[j] + poff + (size_t)me * a.slot_bytes))[e] = x;
+        }
+    }
+    signal_peers(a.sig_peer, a.n, me, blk, epoch, a.light != 0);
+    const bool ok = wait_peers(a.sig_own, a.n, blk, epoch, a.err, a.timeout, a.light != 0);
+    if (ok && a.scan != 2) {
+        const char *arena_own = a.arena_own + poff;
+        // phase B: evaluate my program over the slots of the ranks below me and my own operand
+        // (straight from sendbuf); the program names no rank above me
+        if constexpr (!SMALL)
+        for (size_t i = vb + threadIdx.x; i < ve; i += kThreads) {
+            v4u v[kMaxRanks];
+#pragma unroll
+            for (int j = 0; j < kMaxRanks; ++j)
+                v[j] = (j > me) ? v4u{0, 0, 0, 0} : (j == me) ? send[i] : ld_nt((const v4u *)(arena_own + (size_t)j * a.slot_bytes) + i);
+            // order-free: fold the vectors of the program's leaves in index order
+            if constexpr (Rd::kOrderFree) ((v4u *)a.recv)[i] = vfold_leaves<Rd>(v, a.tp.ps.p[0]);
+            else ((v4u *)a.recv)[i] = vreduce_n<Rd, 4>(v, a.n, a.tp, i * N, 0);
+        }
+        if (blk == 0) {
+            for (size_t e = tail0 + threadIdx.x; e < a.count; e += kThreads) {
+                T col[kMaxRanks];
+#pragma unroll
+                for (int j = 0; j < kMaxRanks; ++j)
+                    col[j] = (j >= me) ? ((const T *)a.send)[e]
+                                       : ld_nt_elem((const T *)(arena_own + (size_t)j * a.slot_bytes) + e);
+                ((T *)a.recv)[e] = prog_eval<Rd>(col, a.tp.ps.p[0]);
+            }
+        }
+    }
+    if (a.dseq) dseq_advance(a.dseq, 1, 0, 1);
+    block_done(a.done);
+}
+
 // One-shot reduce-scatter (small messages): workgroup b pushes, to every peer j, partition b of
 // j's block of my operand, flags, then reduces partition b of my own block from the n slots in
 // program order — the flag it waits for covers exactly the vectors it reads.  Block tails
@@ -477,6 +549,18 @@ struct LOneShot {
             static const int cap2 = resident_grid((const void *)k_oneshot_rs<Rd>, cfg);
             const int g = cfg.grid < cap2 ? cfg.grid : cap2;
             hipLaunchKernelGGL((k_oneshot_rs<Rd>), dim3(g), dim3(kThreads), 0, cfg.stream, a);
+            return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+        }
+        if (a.scan) {
+            // every rank its own program, for order-free ops too (the leaves the program names)
+            if (!prog) return E_ARG;
+            if (a.nvec == 0 && cfg.grid == 1) {
+                hipLaunchKernelGGL((k_oneshot_scan<Rd, true>), dim3(1), dim3(kThreads), 0, cfg.stream, a);
+                return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+            }
+            static const int caps = resident_grid((const void *)k_oneshot_scan<Rd>, cfg);
+            const int g = cfg.grid < caps ? cfg.grid : caps;
+            hipLaunchKernelGGL((k_oneshot_scan<Rd>), dim3(g), dim3(kThreads), 0, cfg.stream, a);
             return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
         }
         if (a.nvec == 0 && cfg.grid == 1) {  // no whole vector: the compact element-wise kernel

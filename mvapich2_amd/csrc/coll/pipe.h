@@ -17,6 +17,8 @@
 //   RS  P1, E, P2 (result -> recvbuf only)
 //   RED P1, E, P2 (root keeps its result, others push to the root), E+1,
 //       root P3
+//   SCAN P1, E, P2 (the owner computes every rank's scan value of the segment: rank r's
+//       -> rank r's AG slot [par][me], its own -> recvbuf), E+1, P3 (k_pipe_scan below)
 //   AG  push my contribution to every AG slot [par][me], E, P3
 //   BC  root: segment j -> rank j's RS slot, its own segment -> every AG
 //       slot; owners forward their segment to every other AG slot (E+1);
@@ -586,9 +588,255 @@ __global__ __launch_bounds__(kPipeThreads) void k_pipe(PipeArgs a) {
     block_done(a.done);
 }
 
+// ---------------------------------------------------------------------------
+// PIPE_SCAN (MPI_Scan / MPI_Exscan): PIPE_AR's phases, flags, parities and slot geometry, with one
+// difference in P2.  Every rank gets a different result from the same operands, so the owner of a
+// segment loads its n columns once and computes every destination rank's value from them: rank
+// r's value goes to rank r's AG slot [par][me], the owner's own value to its recv.  A rank whose
+// program is marked kProgNoResult (MPI_Exscan's rank 0) is pushed nothing, gathers nothing and
+// writes no recv, but raises and awaits every flag like the others.  Per rank this moves (n-1)/n of the operand out in P1 and again in P2, the
+// allreduce's traffic.  A kernel of its own: the allreduce's kernels keep their registers and
+// code, and order-free ops (which have no program instantiation of k_pipe) get only these phases.
+//
+// The n values come from one pass of the reference's recursive-doubling loop in registers
+// (scan_eval: the loop runtime/orders.cpp scan_sym runs symbolically, for a commutative op -- the
+// device reduces builtin ops only), so the ranks share their partials as they do in the reference
+// and every register index is a compile-time constant.  Evaluating each rank's program on its own
+// (a run-time loop over r through prog_eval's select chains) measured 246 us against the
+// allreduce's 115 us for 64 MiB at 2 shared ranks and 2.48 ms against 0.61 ms at 8; this pass
+// needs 36 applies per column at 8 ranks instead of 8 programs of up to 7 selected steps.
+// ---------------------------------------------------------------------------
+template <class Rd, class V>
+__device__ __forceinline__ V scan_apply(V inout, V in) {
+    if constexpr (std::is_same<V, v4u>::value) return vapply<Rd>(inout, in);
+    else return Rd::apply(inout, in);
+}
+
+// recv[r] = rank r's MPI_Scan (excl: MPI_Exscan) result over x[0 .. n), for every r < NM (values of
+// ranks >= n, and an exclusive rank 0's, are not results).  MPIR_Scan_generic scan.c:120-198 /
+// MPIR_Exscan exscan.c:143-214: at mask = 1, 2, 4 rank r with bit `mask` set (dst = r ^ mask is
+// below it) computes partial = uop(in = tmp, inout = partial) and recv = uop(in = tmp, inout =
+// recv) -- Exscan copies its first tmp, which arrives at r's lowest set bit --; a rank below its
+// partner computes partial = uop(in = tmp, inout = partial) when dst = r | mask < n.
+template <class Rd, int NM, class V>
+__device__ __forceinline__ void scan_eval(V (&recv)[NM], const V (&x)[NM], int n, bool excl) {
+    V part[NM];
+#pragma unroll
+    for (int r = 0; r < NM; ++r) part[r] = recv[r] = x[r];
+#pragma unroll
+    for (int mask = 1; mask < NM; mask <<= 1) {
+        if (mask < n) {
+            V prev[NM];
+#pragma unroll
+            for (int r = 0; r < NM; ++r) prev[r] = part[r];
+#pragma unroll
+            for (int r = 0; r < NM; ++r) {
+                if (r & mask) {
+                    const V tmp = prev[r ^ mask];
+                    part[r] = scan_apply<Rd>(prev[r], tmp);
+                    const V acc = scan_apply<Rd>(recv[r], tmp);
+                    recv[r] = (excl && (r & (mask - 1)) == 0) ? tmp : acc;
+                } else if ((r | mask) < NM) {
+                    if ((r | mask) < n) part[r] = scan_apply<Rd>(prev[r], prev[r | mask]);
+                }
+            }
+        }
+    }
+}
+
+// Block-wide: nbytes (whole elements; sources and destinations 16-byte aligned) of the n columns
+// src[j] into every non-null d.p[r] = rank r's destination (r == me: this rank's recv, plain
+// stores).  Software-pipelined like blk_reduce; NM: operand columns held (4 when n <= 4).
+template <class Rd, int U, int NM>
+__device__ __forceinline__ void blk_scan(const PipeArgs &a, const char *const (&src)[kMaxRanks], const Dsts &d,
+                                         size_t nbytes, bool excl) {
+    using T = typename Rd::T;
+    constexpr int N = 16 / sizeof(T);
+    const size_t nv = nbytes >> 4;
+    const int me = a.me;
+    size_t x = threadIdx.x;
+    if (x < nv) {
+        v4u cur[U][NM], nxt[U][NM];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const size_t xu = x + (size_t)u * kPipeThreads;
+#pragma unroll
+            for (int j = 0; j < NM; ++j)
+                cur[u][j] = (j < a.n && xu < nv) ? ld_nt((const v4u *)src[j] + xu) : v4u{0, 0, 0, 0};
+        }
+        for (;;) {
+            const size_t xn = x + (size_t)U * kPipeThreads;
+            const bool more = xn < nv;
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const size_t xu = xn + (size_t)u * kPipeThreads;
+#pragma unroll
+                    for (int j = 0; j < NM; ++j)
+                        nxt[u][j] = (j < a.n && xu < nv) ? ld_nt((const v4u *)src[j] + xu) : v4u{0, 0, 0, 0};
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const size_t xu = x + (size_t)u * kPipeThreads;
+                if (xu < nv) {
+                    v4u res[NM];
+                    scan_eval<Rd, NM>(res, cur[u], a.n, excl);
+#pragma unroll
+                    for (int r = 0; r < NM; ++r)
+                        if (d.p[r]) {
+                            if (r == me || !a.rnt) ((v4u *)d.p[r])[xu] = res[r];  // own recv / plain remote
+                            else st_nt((v4u *)d.p[r] + xu, res[r]);
+                        }
+                }
+            }
+            if (!more) break;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < NM; ++j) cur[u][j] = nxt[u][j];
+            x = xn;
+        }
+    }
+    const size_t tail = (nbytes & 15) / sizeof(T);
+    if (threadIdx.x < tail) {
+        const size_t e = nv * N + threadIdx.x;
+        T col[kMaxRanks], res[kMaxRanks];
+#pragma unroll
+        for (int j = 0; j < kMaxRanks; ++j) col[j] = ld_nt_elem((const T *)(j < a.n ? src[j] : src[0]) + e);
+        scan_eval<Rd, kMaxRanks>(res, col, a.n, excl);
+#pragma unroll
+        for (int r = 0; r < kMaxRanks; ++r)
+            if (d.p[r]) ((T *)d.p[r])[e] = res[r];
+    }
+}
+
+// The same with each destination rank's program evaluated on its own (a.tp.ps.p[r] = rank r's), in
+// a run-time loop over r; the destination table lives in LDS because that loop indexes it.  For
+// the ops whose apply is too large to unroll 36 times (ScanByPrograms below).
+template <class Rd>
+__device__ __forceinline__ void blk_scan_progs(const PipeArgs &a, const char *const (&src)[kMaxRanks], const Dsts &d,
+                                               size_t nbytes) {
+    using T = typename Rd::T;
+    constexpr int N = 16 / sizeof(T);
+    __shared__ char *s_dst[kMaxRanks];
+    const int n = a.n, me = a.me;
+    __syncthreads();  // the previous round's readers of the table are done
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < kMaxRanks; ++j) s_dst[j] = d.p[j];
+    }
+    __syncthreads();
+    const size_t nv = nbytes >> 4;
+    for (size_t x = threadIdx.x; x < nv; x += kPipeThreads) {
+        v4u col[kMaxRanks];
+#pragma unroll
+        for (int j = 0; j < kMaxRanks; ++j) col[j] = j < n ? ld_nt((const v4u *)src[j] + x) : v4u{0, 0, 0, 0};
+#pragma unroll 1
+        for (int r = 0; r < n; ++r) {
+            char *q = s_dst[r];
+            if (!q) continue;
+            const v4u v = vreduce_n<Rd, 4>(col, n, a.tp, 0, r);
+            if (r == me || !a.rnt) ((v4u *)q)[x] = v;
+            else st_nt((v4u *)q + x, v);
+        }
+    }
+    const size_t tail = (nbytes & 15) / sizeof(T);
+    if (threadIdx.x < tail) {
+        const size_t e = nv * N + threadIdx.x;
+        T col[kMaxRanks];
+#pragma unroll
+        for (int j = 0; j < kMaxRanks; ++j) col[j] = ld_nt_elem((const T *)(j < n ? src[j] : src[0]) + e);
+#pragma unroll 1
+        for (int r = 0; r < n; ++r) {
+            char *q = s_dst[r];
+            if (q) ((T *)q)[e] = prog_eval<Rd>(col, a.tp.ps.p[r]);
+        }
+    }
+}
+
+// (op, kind) pairs that take blk_scan_progs: the C99 (Annex G) complex products, whose multiply
+// with its NaN recovery, inlined 36 times by scan_eval, spilled 1490 registers to scratch
+template <class Rd> struct ScanByPrograms : std::false_type {};
+template <int OP, int K>
+struct ScanByPrograms<R<OP, K, void>>
+    : std::integral_constant<bool, OP == OP_PROD && (K == K_CF32_C99 || K == K_CF64_C99)> {};
+
+// P2 of round k.  A scan's segments start on 16-byte boundaries (runtime/coll.cpp even_segments),
+// so the slots carry no misalignment.
+template <class Rd>
+__device__ __forceinline__ void scan_round(const PipeArgs &a, uint64_t round0, int k) {
+    const uint64_t par = (round0 + (uint64_t)k) & 1;
+    const size_t rbase = (size_t)k * a.tseg + (size_t)blockIdx.x * a.tsub;
+    const size_t soff = (size_t)blockIdx.x * a.tsub;
+    const int me = a.me, n = a.n;
+    const size_t len = range_len(a, me, rbase);
+    if (!len) return;
+    const char *src[kMaxRanks];
+    Dsts d{};
+#pragma unroll
+    for (int j = 0; j < kMaxRanks; ++j) {
+        src[j] = (j == me || j >= n) ? a.send + a.seg_off[me] + rbase : pslot(a.rs_peer.p[me], par, j) + soff;
+        if (j < n && a.tp.ps.p[j].res != kProgNoResult)
+            d.p[j] = j == me ? a.recv + a.recv_off[me] + rbase : pslot(a.ag_peer.p[j], par, me) + soff;
+    }
+    const bool excl = a.tp.ps.p[0].res == kProgNoResult;
+    if constexpr (ScanByPrograms<Rd>::value) {
+        blk_scan_progs<Rd>(a, src, d, len);
+    } else if constexpr (WidePipe<Rd>::value) {
+        if (n <= 4) blk_scan<Rd, 2, 4>(a, src, d, len, excl);
+        else blk_scan<Rd, 1, kMaxRanks>(a, src, d, len, excl);
+    } else {
+        blk_scan<Rd, 1, kMaxRanks>(a, src, d, len, excl);
+    }
+}
+
+template <class Rd>
+__global__ __launch_bounds__(kPipeThreads) void k_pipe_scan(PipeArgs a) {
+    uint64_t epoch0 = a.epoch0, round0 = a.round0;
+    if (a.dseq) {
+        const SeqBase q = dseq_read(a.dseq);
+        epoch0 = q.epoch + 1;
+        round0 = q.round;
+    }
+    const int b = blockIdx.x, n = a.n, me = a.me;
+    const unsigned all = (1u << n) - 1u;
+    const bool gathers = a.tp.ps.p[me].res != kProgNoResult;
+    bool ok = true;
+    // PIPE_AR's round structure (pipe_body):
+    //   P1(0) E(0) | wait E(k); P2(k); E(k)+1; P1(k+1); E(k+1); wait E(k)+1; P3(k) |
+    if (a.nrounds > 0) {
+        scatter_round(a, round0, 0);
+        signal_peers(a.sig_peer, n, me, b, epoch0, a.light);
+    }
+    for (int k = 0; k < a.nrounds && ok; ++k) {
+        const uint64_t E = epoch0 + 2 * (uint64_t)k;
+        if (!(ok = wait_mask(a.sig_own, all, b, E, a.err, a.timeout, a.light != 0))) break;
+        scan_round<Rd>(a, round0, k);
+        signal_peers(a.sig_peer, n, me, b, E + 1, a.light);
+        if (k + 1 < a.nrounds) {
+            scatter_round(a, round0, k + 1);
+            signal_peers(a.sig_peer, n, me, b, E + 2, a.light);
+        }
+        // a rank without a result waits too: E(k)+1 is raised after a peer's P3(k-1), and only
+        // behind it may this rank's next call write the AG slots [par(k-1)][me] of its peers
+        if (!(ok = wait_mask(a.sig_own, all, b, E + 1, a.err, a.timeout, a.light != 0))) break;
+        if (!gathers) continue;
+        const size_t rbase = (size_t)k * a.tseg + (size_t)b * a.tsub;
+        gather_slots(a, (round0 + (uint64_t)k) & 1, rbase, (size_t)b * a.tsub, -1);
+    }
+    if (a.dseq) dseq_advance(a.dseq, 2 * (uint64_t)a.nrounds, (uint64_t)a.nrounds, 0);
+    block_done(a.done);
+}
+
 template <int OP, int K>
 struct LPipe {
     static int run(const PipeArgs &a, const LaunchCfg &cfg) {
+        if (a.mode == PIPE_SCAN) {
+            if (a.tp.linear != 4) return E_ARG;
+            hipLaunchKernelGGL((k_pipe_scan<R<OP, K>>), dim3(cfg.grid), dim3(kPipeThreads), 0, cfg.stream, a);
+            return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+        }
         if constexpr (R<OP, K>::kOrderFree)
             hipLaunchKernelGGL((k_pipe<R<OP, K>, false>), dim3(cfg.grid), dim3(kPipeThreads), 0, cfg.stream, a);
         else if (a.tp.linear == 4)

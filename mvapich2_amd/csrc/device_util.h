@@ -45,6 +45,8 @@ struct Prog {
     uint8_t dst[kMaxRanks - 1];
     uint8_t src[kMaxRanks - 1];
 };
+// res of a program that has no result (MPI_Exscan's rank 0): nothing is evaluated or written
+constexpr uint8_t kProgNoResult = 0xff;
 // Programs by element block: element e uses p[min(e / blk, nprog - 1)]
 // (the pof2 blocks of a recursive-halving reduce-scatter, last block takes
 // the remainder, reduce_osu.c:908-910; the n chunks of the ring).
@@ -431,6 +433,26 @@ __device__ __forceinline__ typename Rd::T prog_eval(const typename Rd::T (&v)[kM
     for (int j = 1; j < kMaxRanks; ++j)
         if (p.res == j) out = w[j];
     return out;
+}
+
+// prog_eval's order-free shortcut on whole 16-byte vectors: fold the vectors of the program's
+// leaves in index order (no per-element transpose, so 1-byte types need no scratch memory)
+template <class Rd>
+__device__ __forceinline__ v4u vfold_leaves(const v4u (&v)[kMaxRanks], const Prog &p) {
+    static_assert(Rd::kOrderFree, "order-free ops only");
+    unsigned leaves = p.nsteps ? 0u : 1u << p.res;
+#pragma unroll
+    for (int s = 0; s < kMaxRanks - 1; ++s)
+        if (s < p.nsteps) leaves |= (1u << p.dst[s]) | (1u << p.src[s]);
+    v4u acc = v[0];
+    bool have = false;
+#pragma unroll
+    for (int j = 0; j < kMaxRanks; ++j)
+        if ((leaves >> j) & 1u) {
+            acc = have ? vapply<Rd>(acc, v[j]) : v[j];
+            have = true;
+        }
+    return acc;
 }
 
 __device__ __forceinline__ int prog_block(const ProgSet &ps, size_t e) {

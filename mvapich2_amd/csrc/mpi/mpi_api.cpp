@@ -595,6 +595,55 @@ int PMPI_Allreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype d
 }
 int MPI_Allreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm) WEAK(MPI_Allreduce);
 
+// MPI_Scan / MPI_Exscan.  Checks in the reference's order (scan.c:526-555, exscan.c:343-378):
+// communicator, count, datatype, op handle, a derived type committed, the send buffer (MPI_IN_PLACE
+// is allowed), the receive buffer -- for MPI_Exscan only where rank != 0 --, the op against the
+// type, and last the send buffer aliasing the receive buffer.
+static int scan_call(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm,
+                     bool excl, const char *fn) {
+    const bool recv_matters = !excl || comm_index(comm) < 0 || comm_rank_of(comm) != 0;
+    int brc = null_userbuf(sendbuf, count, dt) ? MPI_ERR_BUFFER : MPI_SUCCESS;
+    if (!brc && recv_matters && (inplace_buf(recvbuf, count) || null_userbuf(recvbuf, count, dt))) brc = MPI_ERR_BUFFER;
+    int rc = coll_checks(comm, count, dt, op, brc);
+    if (!rc && sendbuf != MPI_IN_PLACE && count != 0 && sendbuf == recvbuf) rc = MPI_ERR_BUFFER;
+    if (rc) return err_return(comm, rc, fn);
+    if (count == 0) return MPI_SUCCESS;
+    if (comm == MPI_COMM_SELF) {  // one rank: Scan copies, Exscan leaves recvbuf alone
+        if (!excl && sendbuf != MPI_IN_PLACE) {
+            const long span = dtype_span(dt, count);
+            rc = is_dev(recvbuf) || is_dev(sendbuf) ? mv2h_memcpy_dtod(recvbuf, sendbuf, span) : (memcpy(recvbuf, sendbuf, span), 0);
+        }
+        return err_return(comm, rc, fn);
+    }
+    // several nodes: the SMP-aware shape (scan.c:267-406) is not built; refused from the job's
+    // shape alone, on every rank, before any device or network work
+    if (world().nnodes > 1) {
+        MV2_ERR("%s: only jobs on one node are supported (this job spans %d nodes)", fn, world().nnodes);
+        return err_return(comm, MPI_ERR_OTHER, fn);
+    }
+    if (UserOp *u = user_op(op))
+        return err_return(comm, host_scan(sendbuf, recvbuf, count, dt, HostOp{u->fn, u->commute ? OPK_USER_COMM : OPK_USER_NONCOMM}, excl), fn);
+    if (is_x87(dt) && op_index(op) < OP_REPLACE) {
+        g_ld_op = op_index(op);
+        return err_return(comm, host_scan(sendbuf, recvbuf, count, dt, HostOp{ld_uop, OPK_BUILTIN}, excl), fn);
+    }
+    rc = excl ? mv2h_exscan(sendbuf, recvbuf, (size_t)count, dt, op, nullptr)
+              : mv2h_scan(sendbuf, recvbuf, (size_t)count, dt, op, nullptr);
+    return err_return(comm, rc, fn);
+}
+
+int PMPI_Scan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return scan_call(sendbuf, recvbuf, count, dt, op, comm, false, "MPI_Scan");
+}
+int MPI_Scan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm) WEAK(MPI_Scan);
+
+int PMPI_Exscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return scan_call(sendbuf, recvbuf, count, dt, op, comm, true, "MPI_Exscan");
+}
+int MPI_Exscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm) WEAK(MPI_Exscan);
+
 int PMPI_Reduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, int root, MPI_Comm comm) {
     std::lock_guard<std::recursive_mutex> lk(g_cs);
     const char *fn = "MPI_Reduce";
@@ -1114,6 +1163,24 @@ int PMPI_Iallreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype 
 }
 int MPI_Iallreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm,
                    MPI_Request *request) WEAK(MPI_Iallreduce);
+
+// the schedules make MPIR_Scan_generic's / MPIR_Exscan's calls in the same order (iscan.c:72-160,
+// iexscan.c): the blocking programs
+int PMPI_Iscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm,
+               MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Iscan", [&] { return PMPI_Scan(sendbuf, recvbuf, count, dt, op, comm); });
+}
+int MPI_Iscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm,
+              MPI_Request *request) WEAK(MPI_Iscan);
+
+int PMPI_Iexscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm,
+                 MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Iexscan", [&] { return PMPI_Exscan(sendbuf, recvbuf, count, dt, op, comm); });
+}
+int MPI_Iexscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, MPI_Comm comm,
+                MPI_Request *request) WEAK(MPI_Iexscan);
 
 int PMPI_Ireduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op, int root, MPI_Comm comm,
                  MPI_Request *request) {

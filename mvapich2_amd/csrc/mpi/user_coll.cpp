@@ -431,11 +431,13 @@ int collect_results(const char *res_mine, char *res_all, long U, long chunk, siz
     return rc ? MPI_ERR_OTHER : 0;
 }
 
-// root < 0: every rank delivers the result; root >= 0: the root only
+// root < 0: every rank delivers the result; root >= 0: the root only.  no_result: this rank stages
+// its operand like every other and delivers nothing (MPI_Exscan's rank 0; sp.U == 0 only, where no
+// rank evaluates a part for another)
 int run_split(const void *src, int count, const Typed &t, const Split &sp, MPI_User_function *fn, void *recvbuf,
-              int root) {
+              int root, bool no_result = false) {
     const int n = job().n, me = job().me;
-    const bool deliver = root < 0 || me == root;
+    const bool deliver = !no_result && (root < 0 || me == root);
     PhaseClock pc;
     Operands ou{}, oo{};
     int rc = stage_split(src, count, t, sp, ou, oo);
@@ -1061,6 +1063,27 @@ int host_reduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, 
     if ((rc = plan_reduce(n, root, root, (size_t)count, (int)t.tsize, (int)t.extent, &pr, op.opk))) return rc;
     const Split sp{&pr.ps, count, &pr.ps, 0};
     return run_split(src, count, t, sp, op.fn, recvbuf, root);
+}
+
+// MPI_Scan / MPI_Exscan (MPIR_Scan_generic scan.c:73-213, MPIR_Exscan exscan.c:95-220): where the
+// programs differ between ranks -- every rank's result is its own tree, the non-commutative
+// branch keeping the lower ranks on the left -- so nothing is split: every rank fetches the
+// whole operands and evaluates its own program.  A rank without a result (MPI_Exscan's rank 0)
+// takes part in the operands' allgather and delivers nothing.
+int host_scan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, const HostOp &op, bool exclusive) {
+    const World &w = world();
+    const Typed t = typed(dt);
+    if (t.tsize < 0 || t.extent < 0) return MPI_ERR_TYPE;
+    if (w.nnodes > 1) return MPI_ERR_OTHER;
+    const int n = w.size, me = w.rank;
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    const void *src = in_place ? recvbuf : sendbuf;
+    if (n == 1) return exclusive || in_place ? MPI_SUCCESS : copy_typemap(src, recvbuf, count, t);
+    Plan p;
+    if (const int rc = plan_scan(n, me, (size_t)count, exclusive, op.opk, &p)) return rc;
+    const bool none = p.ps.p[0].res == kProgNoResult;
+    const Split sp{&p.ps, 0, &p.ps, 0};
+    return run_split(src, count, t, sp, op.fn, recvbuf, -1, none);
 }
 
 // Reduce_scatter: the order of MPIR_Reduce_scatter_MV2's choice for this rank's block — ring,

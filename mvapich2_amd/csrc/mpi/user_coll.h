@@ -37,5 +37,8 @@ struct HostOp {
 int host_allreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, const HostOp &op);
 int host_reduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, const HostOp &op, int root);
 int host_reduce_scatter(const void *sendbuf, void *recvbuf, const int *counts, MPI_Datatype dt, const HostOp &op);
+// MPI_Scan / MPI_Exscan on one node: every rank evaluates its own program (orders.h plan_scan)
+// over the allgathered operands; MPI_Exscan's rank 0 stages its operand and writes nothing
+int host_scan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, const HostOp &op, bool exclusive);
 
 }  // namespace mv2

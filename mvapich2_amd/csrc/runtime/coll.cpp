@@ -658,6 +658,7 @@ static int oneshot_grid(size_t nvec, int gcap) {
 // probe run on this node's world, before any inter-node link exists
 extern "C" {
 static int allreduce_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);
+static int scan_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream, bool excl);
 }
 
 namespace mv2 {
@@ -920,6 +921,7 @@ int mv2h_get_info(const char *key, long *value) {
     else if (!strcmp(key, "hip_init_us")) *value = (long)(w.hip_init_ms * 1e3 + 0.5);
     else if (!strcmp(key, "code_load_us")) *value = (long)(w.code_load_ms * 1e3 + 0.5);
     else if (!strcmp(key, "selftest_calls")) *value = w.selftest_calls;
+    else if (!strcmp(key, "selftest_scan_calls")) *value = w.selftest_scan_calls;
     else if (!strcmp(key, "call_allocs")) *value = (long)w.call_allocs;
     else if (!strcmp(key, "pool_trims")) *value = (long)w.pool_trims;
     else if (!strcmp(key, "rl_tiny_max")) *value = (long)w.rl_tiny_max;
@@ -1226,6 +1228,16 @@ int mv2h_plan(int coll, int n, int rank, int root, size_t count, const size_t *c
         if (!counts) return E_ARG;
         rc = plan_reduce_scatter(n, rank, counts, dt->size, dt->extent, &p, opkind);
         break;
+    case MV2H_COLL_SCAN:
+    case MV2H_COLL_EXSCAN:
+        rc = plan_scan(n, rank, count, coll == MV2H_COLL_EXSCAN, opkind, &p);
+        break;
+    case MV2H_COLL_SCAN_ALL:
+    case MV2H_COLL_EXSCAN_ALL:
+        memset(&p, 0, sizeof(p));
+        p.algo = coll == MV2H_COLL_EXSCAN_ALL ? ALG_EXSCAN_RD : ALG_SCAN_RD;
+        rc = scan_progs(n, coll == MV2H_COLL_EXSCAN_ALL, opkind, &p.ps);
+        break;
     default: return E_ARG;
     }
     if (rc) return rc;
@@ -1495,6 +1507,96 @@ int mv2h_allreduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, 
     const int rc = allreduce_entry(sendbuf, recvbuf, count, dtype, op, stream);
     pvar_end(rc == 0);
     return rc;
+}
+
+// MPI_Scan / MPI_Exscan over this node's ranks (orders.cpp plan_scan: MPIR_Scan_generic /
+// MPIR_Exscan, one algorithm at every size).  Every rank gets a different tree over the same
+// operands.  Small messages: the one-shot scan kernel with this rank's own program, its operand
+// pushed only to the ranks above it.  Larger ones: PIPE_SCAN, where the owner of a segment
+// computes every rank's value in one pass of the reference's loop and reads from the table of all
+// ranks' programs only which ranks have a result (coll/pipe.h).  The crossover is the allreduce's (oneshot_max),
+// unmeasured for scans.  MPI_Exscan's rank 0 takes part in every push and flag but has no result:
+// its recvbuf is never written, staged or not.
+static int scan_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream, bool excl) {
+    hp_entry();
+    const DtypeInfo *dt = nullptr;
+    int rc = check_op_dtype(op, dtype, &dt);
+    if (rc) return rc;
+    if (count == 0) return 0;
+    if ((rc = kind_supported(dt))) return rc;
+    if ((rc = require_world())) return rc;
+    World &w = world();
+    const int n = w.size, me = w.rank, oi = op_index(op);
+    if (oi >= OP_REPLACE) {
+        MV2_ERR("MPI_%s: MPI_REPLACE / MPI_NO_OP are not supported", excl ? "Exscan" : "Scan");
+        return E_OP;
+    }
+    hipStream_t st = pick_stream(stream);
+    const size_t bytes = count * (size_t)dt->extent;
+    const bool in_place = sendbuf == (const void *)-1 || sendbuf == recvbuf;
+    const bool no_result = excl && me == 0;
+    if (n == 1) {  // Scan copies, Exscan does nothing
+        if (!excl && !in_place && hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDefault, st) != hipSuccess)
+            return E_INTERN;
+        return finish(st, false);
+    }
+    Staged s;
+    if ((rc = stage_in(sendbuf, recvbuf, bytes, bytes, in_place, st, s))) return rc;
+    if (no_result) s.copy_back = false;
+    TreeParams tp = tree_base(n);
+    tp.linear = 4;
+    if (bytes <= w.oneshot_max && bytes <= w.slot_bytes) {
+        Plan p;
+        if ((rc = plan_scan(n, me, count, excl, OPK_BUILTIN, &p))) return rc;
+        log_plan(excl ? "exscan" : "scan", p, count);
+        tp.ps = p.ps;
+        OneShotArgs a{};
+        oneshot_common(a, st);
+        a.send = s.send;
+        a.recv = s.recv;
+        a.count = count;
+        static const long scalar_max = env_long_coll("MV2AMD_AR_SCALAR_MAX", 1024);
+        a.nvec = bytes <= (size_t)scalar_max ? 0 : bytes / 16;
+        a.tp = tp;
+        a.scan = no_result ? 2 : 1;
+        LaunchCfg cfg = coll_cfg(oneshot_grid(a.nvec, grid_cap()), st);
+        tmark0(st);
+        rc = launch_oneshot(oi, dt->kind, a, dt->extent, cfg);
+        tmark1(st);
+    } else {
+        if ((rc = scan_progs(n, excl, OPK_BUILTIN, &tp.ps))) return rc;
+        MV2_DEBUG("%s count %zu -> pipelined %s", excl ? "exscan" : "scan", count, algo_name(excl ? ALG_EXSCAN_RD : ALG_SCAN_RD));
+        PipeArgs a{};
+        a.mode = PIPE_SCAN;
+        a.send = s.send;
+        a.recv = s.recv;
+        a.esize = dt->extent;
+        even_segments(a, bytes, n);
+        a.tp = tp;
+        rc = run_pipe(a, oi, dt, st);
+    }
+    if (rc) return rc;
+    if ((rc = stage_out(s, st))) return rc;
+    return finish(st, w.timing);
+}
+
+// Several nodes: the reference's SMP-aware shape (scan.c:267-406: a scan per node, a scan over the
+// node leaders, a broadcast of the lower nodes' total and one more uop) is not built; both calls
+// are refused on every rank from the job's shape alone, before any device or network work.
+static int scan_one_node_only(const char *name) {
+    if (world().nnodes <= 1) return 0;
+    MV2_ERR("%s: only jobs on one node are supported (this job spans %d nodes)", name, world().nnodes);
+    return E_OTHER;
+}
+
+int mv2h_scan(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream) {
+    if (int rc = scan_one_node_only("MPI_Scan")) return rc;
+    return scan_entry(sendbuf, recvbuf, count, dtype, op, stream, false);
+}
+
+int mv2h_exscan(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream) {
+    if (int rc = scan_one_node_only("MPI_Exscan")) return rc;
+    return scan_entry(sendbuf, recvbuf, count, dtype, op, stream, true);
 }
 
 // forced: the programs to run instead of the one-node selection's (a node step of
@@ -3316,7 +3418,7 @@ namespace mv2 {
 //   allreduce (small rounds: both parities inside one call) x 2, pipelined reduce-scatter,
 //   allgather and broadcast x 2 each, one-shot allgather and broadcast x 2 each, and, with the
 //   graph lane, a captured one-shot and a captured pipelined allreduce replayed 3 times each (its
-//   own arenas and device sequence).
+//   own arenas and device sequence); a one-shot and a pipelined scan (counted apart).
 // The per-call mismatch counts are read once at the end; the verdict is agreed through the
 // host control segment.  On a mismatch every rank falls back to the full system-scope release
 // and runs the whole set again; a second failure fails MPI_Init instead of returning wrong
@@ -3340,7 +3442,7 @@ int coll_selftest() {
     }
     hipStream_t st = w.stream;
     const char *what[kMaxCalls] = {};
-    int verdict = 0, calls = 0;
+    int verdict = 0, calls = 0, scan_calls = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         hipMemsetAsync(bad, 0, kMaxCalls * 4, st);
         int rc = 0;
@@ -3351,7 +3453,7 @@ int coll_selftest() {
         // capture once ran 8 K elements past the end)
         auto fits = [&](const uint32_t *p, size_t c) {
             const uint32_t *b = (p >= rb && p < rb + cap) ? rb : sb;
-            if (p < b || (size_t)(p - b) + c > cap || calls > kMaxCalls) {
+            if (p < b || (size_t)(p - b) + c > cap || calls + scan_calls > kMaxCalls) {
                 MV2_ERR("self-test: call %d does not fit its buffers (%zu elements at +%td of %zu)", calls, c, p - b, cap);
                 if (!rc) rc = E_INTERN;
                 return false;
@@ -3466,6 +3568,23 @@ int coll_selftest() {
             check(rb, c, k, 1, root, 0, "pipelined broadcast");
         }
         w.oneshot_max = os_keep;
+        // scan: one small (one-shot) and one pipelined MPI_Scan; rank me's element is the sum over
+        // ranks 0 .. me.  Counted apart (selftest_scan_calls), their mismatch words taken from the
+        // top of `bad`
+        {
+            const size_t sc_sizes[2] = {1027, ((size_t)1 << 18) + 5};
+            scan_calls = 0;
+            for (int i = 0; i < 2 && !rc; ++i) {
+                const int k = kMaxCalls - 1 - scan_calls++;
+                if (i == 1) w.oneshot_max = 0;
+                fill(sb, sc_sizes[i], k, me);
+                if (!rc) rc = ::scan_entry(sb, rb, sc_sizes[i], MPI_INT_H, MPI_SUM_H, nullptr, false);
+                if (!rc && fits(rb, sc_sizes[i]))
+                    rc = launch_selftest_check(rb, sc_sizes[i], seed_of(k), me + 1, 0, 0, 0, bad + k, st);
+                what[k] = i ? "pipelined scan" : "one-shot scan";
+            }
+            w.oneshot_max = os_keep;
+        }
         // graph lane: a captured one-shot and a captured pipelined allreduce, replayed
         if (w.graph_lane && !rc) {
             hipStream_t cs = nullptr;
@@ -3511,8 +3630,8 @@ int coll_selftest() {
         if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(hb, bad, sizeof(hb), hipMemcpyDeviceToHost) != hipSuccess)
             rc = rc ? rc : E_INTERN;
         int ok = rc == 0;
-        for (int k = 0; k < calls && ok; ++k)
-            if (hb[k]) {
+        for (int k = 0; k < kMaxCalls && ok; ++k)
+            if ((k < calls || k >= kMaxCalls - scan_calls) && hb[k]) {
                 MV2_ERR("self-test (%s release): call %d (%s) returned %u wrong elements",
                         w.light_release ? "light" : "full", k, what[k] ? what[k] : "?", hb[k]);
                 ok = 0;
@@ -3545,6 +3664,7 @@ int coll_selftest() {
         }
     }
     w.selftest_calls = calls;
+    w.selftest_scan_calls = scan_calls;
     hipFree(sb);
     hipFree(rb);
     hipFree(bad);

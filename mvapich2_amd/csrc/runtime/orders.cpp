@@ -139,7 +139,7 @@ const char *algo_name(int a) {
     static const char *names[ALG_COUNT] = {
         "none", "shmem_linear", "pt2pt_rs", "pt2pt_rd", "ring_wrapper", "topo_tree", "two_level_p2p",
         "binomial", "knomial", "redscat_gather", "rs_ring", "rs_rec_halving", "rs_pairwise", "rs_basic",
-        "reduce_topo", "rs_noncomm_pof2", "rs_noncomm_rd"};
+        "reduce_topo", "rs_noncomm_pof2", "rs_noncomm_rd", "scan_rd", "exscan_rd"};
     return (a >= 0 && a < ALG_COUNT) ? names[a] : "?";
 }
 
@@ -1215,6 +1215,65 @@ int plan_binomial(int n, int root, Plan *p, bool noncomm) {
     memset(p, 0, sizeof(*p));
     if (n <= 1) return 0;
     return reduce_fill(p, ALG_BINOMIAL, n, root, 0, 0, noncomm);
+}
+
+// ---------------------------------------------------------------------------
+// MPI_Scan / MPI_Exscan
+// ---------------------------------------------------------------------------
+// MPIR_Scan_generic (scan.c:120-198) and MPIR_Exscan (exscan.c:143-214): partial = recv = x_r; at
+// mask = 1, 2, 4 ... every rank exchanges its partial with dst = r ^ mask (skipped when dst >= n).
+// r > dst: partial = uop(in = tmp, inout = partial) and recv = uop(in = tmp, inout = recv) -- for
+// Exscan the first tmp is copied into recv instead (exscan.c:179-193).  r < dst: partial =
+// uop(in = tmp, inout = partial) for a commutative op, else tmp = uop(in = partial, inout = tmp)
+// and partial = tmp, which keeps the lower ranks on the left (scan.c:177-190).  recv[r] = -1: no result.
+static void scan_sym(Sym &s, int n, bool exclusive, bool noncomm, std::vector<int> &recv) {
+    std::vector<int> partial(n);
+    recv.assign(n, -1);
+    for (int r = 0; r < n; ++r) {
+        partial[r] = s.leaf(r);
+        if (!exclusive) recv[r] = partial[r];
+    }
+    for (int mask = 1; mask < n; mask <<= 1) {
+        const std::vector<int> prev = partial;
+        for (int r = 0; r < n; ++r) {
+            const int dst = r ^ mask;
+            if (dst >= n) continue;
+            const int tmp = prev[dst];
+            if (r > dst) {
+                partial[r] = s.op(prev[r], tmp);
+                recv[r] = recv[r] < 0 ? tmp : s.op(recv[r], tmp);
+            } else {
+                partial[r] = noncomm ? s.op(tmp, prev[r]) : s.op(prev[r], tmp);
+            }
+        }
+    }
+}
+
+int scan_progs(int n, bool exclusive, int opk, ProgSet *ps) {
+    memset(ps, 0, sizeof(*ps));
+    if (n < 1 || n > kMaxRanks) return E_ARG;
+    Sym s;
+    std::vector<int> recv;
+    scan_sym(s, n, exclusive, opk == OPK_USER_NONCOMM, recv);
+    ps->nprog = n;
+    ps->blk = ~(uint64_t)0 >> 1;
+    for (int r = 0; r < n; ++r) {
+        if (recv[r] < 0) ps->p[r].res = kProgNoResult;
+        else if (!s.compile(recv[r], ps->p[r])) return E_INTERN;
+    }
+    return 0;
+}
+
+int plan_scan(int n, int me, size_t count, bool exclusive, int opk, Plan *p) {
+    (void)count;  // one algorithm at every size
+    memset(p, 0, sizeof(*p));
+    if (me < 0 || me >= n) return E_ARG;
+    ProgSet all;
+    const int rc = scan_progs(n, exclusive, opk, &all);
+    if (rc) return rc;
+    p->algo = exclusive ? ALG_EXSCAN_RD : ALG_SCAN_RD;
+    single(p->ps, all.p[me]);
+    return 0;
 }
 
 int plan_reduce_scatter(int n, int me, const size_t *counts, int tsize, int textent, Plan *p, int opk) {

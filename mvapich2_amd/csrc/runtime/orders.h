@@ -38,6 +38,8 @@ enum Algo : int {
     ALG_REDUCE_TOPO = 14,    // MPIR_Reduce_topo_aware_hierarchical_MV2 (reduce_osu.c:206)
     ALG_RS_NONCOMM_POF2 = 15,// MPIR_Reduce_scatter_noncomm_MV2 (red_scat_osu.c:132): pof2, equal counts
     ALG_RS_NONCOMM_RD = 16,  // MPIR_Reduce_scatter_non_comm_MV2's recursive doubling (:1478)
+    ALG_SCAN_RD = 17,        // MPIR_Scan_generic (scan.c:73-213): recursive doubling, one result per rank
+    ALG_EXSCAN_RD = 18,      // MPIR_Exscan (exscan.c:95-220): the same loop, own operand left out
     ALG_COUNT
 };
 
@@ -171,6 +173,17 @@ struct ExprNode {
     int leaf, a, b;
 };
 int rs_noncomm_expr(int n, int me, bool pof2_equal, std::vector<ExprNode> &nodes);
+
+// MPI_Scan / MPI_Exscan over the n ranks of one node: MPIR_Scan_generic (scan.c:73-213; on one node
+// MPIR_Scan's intranode step is the whole call and lands there, scan.c:225-406) and MPIR_Exscan
+// (exscan.c:95-220).  Every rank's result is a tree of its own over x_0 .. x_me (Exscan: x_0 ..
+// x_{me-1}); the nonblocking schedules (iscan.c:72-160, iexscan.c) make the same calls in the same
+// order.  Exscan's rank 0 has no result: its program is marked res = kProgNoResult (device_util.h),
+// "write nothing".
+// plan_scan fills out->ps with rank me's program; scan_progs fills ps->p[r] with rank r's, nprog = n
+// (indexed by destination rank, not by element block: the pipelined kernel evaluates all of them).
+int plan_scan(int n, int me, size_t count, bool exclusive, int opk, Plan *out);
+int scan_progs(int n, bool exclusive, int opk, ProgSet *ps);
 
 // Nonblocking collectives.  While a nonblocking call is being initiated
 // (nbc_set(kind) on this thread), plan_allreduce / plan_reduce /

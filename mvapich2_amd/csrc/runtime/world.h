@@ -178,6 +178,7 @@ struct World {
     // library (loads its gfx950 code object: HIP defers that to the first launch)
     double hip_init_ms = 0, code_load_ms = 0;
     int selftest_calls = 0;  // collective calls MPI_Init's self-test checked (all ranks, every element)
+    int selftest_scan_calls = 0;  // MPI_Scan calls it checked besides (counted apart)
     // device allocations made inside MPI calls (scratch growth: hipMalloc, each paired with a
     // hipFree that synchronises the device); stays flat once the scratch caches are warm
     uint64_t call_allocs = 0;

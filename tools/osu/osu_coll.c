@@ -6,7 +6,7 @@
  * report the average over ranks of per-rank mean latency), with `-d rocm`
  * device buffers and busbw columns added (OMB prints latency only).
  *
- *   osu_coll -c allreduce|reduce|reduce_scatter|allgather|bcast|reduce_local|latency|bw|all
+ *   osu_coll -c allreduce|reduce|scan|exscan|reduce_scatter|allgather|bcast|reduce_local|latency|bw|all
  *            [-m min:max bytes] [-f size factor (2)] [-i iters] [-I large-message iters]
  *            [-x warmup] [-C cap bytes for -c all's reduce_scatter/allgather/bcast]
  *            [-d rocm|host] [-v (validate every collective)] [-j (JSON rows)]
@@ -109,6 +109,11 @@ static int check(const char *c, const void *rbuf, size_t count, size_t sz, int r
     if (!strcmp(c, "allreduce")) {
         const float *f = (const float *)h;
         for (size_t i = 0; i < count && ok; ++i) ok = f[i] == (float)(i % 100 + 1) * tot;
+    } else if (!strcmp(c, "scan") || !strcmp(c, "exscan")) {
+        /* ranks 0 .. rank (exscan: .. rank - 1; rank 0 has no result) */
+        const int top = !strcmp(c, "scan") ? rank + 1 : rank;
+        const float *f = (const float *)h;
+        for (size_t i = 0; i < count && ok && top > 0; ++i) ok = f[i] == (float)(i % 100 + 1) * (float)(top * (top + 1) / 2);
     } else if (!strcmp(c, "reduce_scatter")) {
         size_t off = 0;
         for (int r = 0; r < rank; ++r) off += (size_t)counts[r];
@@ -155,6 +160,8 @@ static int run_coll(const char *c, int rank, int size, void *sbuf, void *rbuf, s
             double t0 = MPI_Wtime();
             if (!strcmp(c, "allreduce")) rc |= MPI_Allreduce(sbuf, rbuf, (int)count, MPI_FLOAT, MPI_SUM, MPI_COMM_WORLD);
             else if (!strcmp(c, "reduce")) rc |= MPI_Reduce(sbuf, rbuf, (int)count, MPI_FLOAT, MPI_SUM, 0, MPI_COMM_WORLD);
+            else if (!strcmp(c, "scan")) rc |= MPI_Scan(sbuf, rbuf, (int)count, MPI_FLOAT, MPI_SUM, MPI_COMM_WORLD);
+            else if (!strcmp(c, "exscan")) rc |= MPI_Exscan(sbuf, rbuf, (int)count, MPI_FLOAT, MPI_SUM, MPI_COMM_WORLD);
             else if (!strcmp(c, "reduce_local")) rc |= MPI_Reduce_local(sbuf, rbuf, (int)count, MPI_FLOAT, MPI_SUM);
             /* osu_reduce_scatter.c:116-131: size/n each, first size%n ranks one more */
             else if (!strcmp(c, "reduce_scatter")) rc |= MPI_Reduce_scatter(sbuf, rbuf, counts, MPI_FLOAT, MPI_SUM, MPI_COMM_WORLD);
