@@ -283,7 +283,8 @@ int mv2h_set_tuning(const char *key, long value);
  * wall time and its parts), "selftest_calls" (collective calls MPI_Init's self-test checked),
  * "call_allocs" (device allocations made inside MPI calls: scratch growth, pooled temporaries),
  * "hw_queues_set" (GPU_MAX_HW_QUEUES set before HIP started; negative: wanted, but HIP was already
- * running) */
+ * running), "rl_tiny_max" / "rl_grid" / "max_grid" (the launch tunings of the same names as they stand:
+ * mv2h_set_tuning, MV2AMD_RL_TINY_MAX / MV2AMD_RL_GRID) */
 int mv2h_get_info(const char *key, long *value);
 
 #ifdef __cplusplus

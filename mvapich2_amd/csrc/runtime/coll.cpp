@@ -925,6 +925,8 @@ int mv2h_get_info(const char *key, long *value) {
     else if (!strcmp(key, "call_allocs")) *value = (long)w.call_allocs;
     else if (!strcmp(key, "pool_trims")) *value = (long)w.pool_trims;
     else if (!strcmp(key, "rl_tiny_max")) *value = (long)w.rl_tiny_max;
+    else if (!strcmp(key, "rl_grid")) *value = w.rl_grid;
+    else if (!strcmp(key, "max_grid")) *value = w.max_grid;
     else if (!strcmp(key, "aql_calls")) *value = (long)w.aql_calls;
     else if (!strcmp(key, "aql_kernels")) *value = aql_kernels();
     else if (!strcmp(key, "aql_acquire")) *value = aql_acquire_scope();
