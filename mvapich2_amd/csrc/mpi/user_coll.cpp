@@ -28,7 +28,7 @@
 //
 // Several nodes.  The operands travel the same way over the whole job (the packed allgather
 // crosses the leaders' links) and the schedule is the one the device path restates there
-// (runtime/coll.cpp mn_host_schedule): flat schedules are evaluated as above over the job's ranks;
+// (runtime/coll_mn.cpp mn_host_schedule): flat schedules are evaluated as above over the job's ranks;
 // a two-level schedule is evaluated in its two stages — each node's partial at its leader (the
 // node step's programs over that node's operands), then the leaders' programs over the partials.
 #include "user_coll.h"
@@ -1097,7 +1097,7 @@ int host_reduce_scatter(const void *sendbuf, void *recvbuf, const int *counts, M
     const Typed t = typed(dt);
     if (t.tsize < 0 || t.extent <= 0) return MPI_ERR_TYPE;
     const int n = J.n, me = J.me;
-    // across nodes MV2AMD_MN_PROG_MAX may lower the programs' limit (runtime/coll.cpp mn_prog_max)
+    // across nodes MV2AMD_MN_PROG_MAX may lower the programs' limit (runtime/world.cpp mn_prog_max)
     const int pm = world().nnodes > 1 ? mn_prog_max() : kMaxRanks;
     long total = 0, disp = 0;
     std::vector<size_t> cz(n);

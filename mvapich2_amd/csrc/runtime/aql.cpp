@@ -265,7 +265,7 @@ int aql_reduce_local(int op, int kind, const void *in, void *io, size_t count, s
             (void)hipGetLastError();
             if (hipStreamSynchronize(w.stream) != hipSuccess) return 0;
         }
-        w.stream_hip_busy = false;  // until the next launch on it (coll.cpp pick_stream)
+        w.stream_hip_busy = false;  // until the next launch on it (call.cpp pick_stream)
     }
     if (g_aql.stream_checks && hipStreamQuery(nullptr) != hipSuccess) {
         (void)hipGetLastError();

@@ -1,0 +1,67 @@
+// coll_internal.h — what the files of the collective runtime share: call.cpp (a call's stream,
+// timing marks, completion and error word), coll_node.cpp (the one-node collectives), coll_mn.cpp
+// (across nodes), coll_init.cpp (MPI_Init's tuning and self-test), coll.cpp (the mv2h_* C-ABI).
+#pragma once
+#include "world.h"
+
+namespace mv2 {
+
+// ---- call.cpp ----
+hipStream_t pick_stream(void *s);
+void stream_tail(hipStream_t st);
+uint64_t now_ns();
+void hp_entry();  // a new API call
+Done arm_done(hipStream_t st);
+void withhold_done(int k);  // test hooks (mv2h_set_tuning)
+void fake_split(int k);
+hipError_t enq_copy(void *dst, const void *src, size_t bytes, hipStream_t st);
+hipError_t enq_copy_last(void *dst, const void *src, size_t bytes, hipStream_t st);
+hipError_t settle_split(hipStream_t st);
+hipError_t wait_done(hipStream_t st, uint64_t want);
+void log_epochs(uint64_t lo, uint64_t hi, hipStream_t st);
+int check_err_word();
+int finish(hipStream_t st, bool timed);
+void tmark0(hipStream_t st);
+void tmark1(hipStream_t st);
+int is_device(const void *p);
+int kind_supported(const DtypeInfo *dt);
+int check_op_dtype(int op, int dtype, const DtypeInfo **out);
+
+// ---- coll_node.cpp: the collectives over this node's ranks ----
+TreeParams tree_base(int n);
+void log_plan(const char *coll, const Plan &p, size_t count);
+long ar_scalar_max();  // MV2AMD_AR_SCALAR_MAX / MV2AMD_RS_SCALAR_MAX
+long rs_scalar_max();
+int allreduce_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);
+int node_allreduce_intra(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream, int intra);
+int scan_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream, bool excl);
+int reduce_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, int root, void *stream,
+                 const Plan *forced = nullptr);
+int reduce_scatter_entry(const void *sendbuf, void *recvbuf, const size_t *recvcounts, int dtype, int op, void *stream);
+int allgather_node(const void *sendbuf, void *recvbuf, size_t bytes, void *stream);
+int bcast_node(void *buffer, size_t bytes, int root, void *stream);
+
+// ---- coll_mn.cpp: the collectives of a job on several nodes ----
+int mn_allreduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);
+int mn_reduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, int root, void *stream);
+int mn_reduce_scatter(const void *sendbuf, void *recvbuf, const size_t *recvcounts, int dtype, int op, void *stream);
+int mn_allgather(const void *sendbuf, void *recvbuf, size_t bytes, void *stream);
+int mn_bcast(void *buffer, size_t bytes, int root, void *stream);
+int mn_allreduce_route(int ppn, int gsize, long nbytes, size_t count, bool in_place, int nbc, int *intra, int *inter,
+                       int *sel_out, int *rem_route);
+int mn_reduce_route(int ppn, int gsize, size_t count, int tsize, int nbc);
+int mn_reduce_scatter_route(int gsize, long nbytes);
+
+// a stream-ordered call (mv2h_*_enqueue); graph: one being captured into a HIP graph
+struct EnqueueScope {
+    explicit EnqueueScope(bool graph = false) {
+        world().enqueue = true;
+        world().graph = graph;
+    }
+    ~EnqueueScope() {
+        world().enqueue = false;
+        world().graph = false;
+    }
+};
+
+}  // namespace mv2

@@ -780,7 +780,7 @@ static int plan_allreduce_build(int n, int me, size_t count, int tsize, int text
         n <= K.allred_ring_ppn) {
         p->algo = ALG_RING;
         if (count >= (size_t)n && !in_place) return prog_ring_allreduce(n, (count / n) * n, p->ps) ? 0 : E_INTERN;
-        return 0;  // the wrapper runs pt2pt_rs (count < n, or MPI_IN_PLACE): see coll.cpp
+        return 0;  // the wrapper runs pt2pt_rs (count < n, or MPI_IN_PLACE): see coll_node.cpp
     }
     // tuning tables (:3162-3373)
     const AllreduceEntry &e = ppn_conf(n) == 1 ? kAr2 : kAr16;

@@ -202,7 +202,7 @@ void nbc_set(int kind);
 int nbc_kind();
 
 // Several nodes: the schedule of a host-evaluated reduction (user MPI_Op, x87 types) over the job,
-// as runtime/coll.cpp restates it for the device path (mn_select, MPIR_Allreduce_two_level_MV2,
+// as runtime/coll_mn.cpp restates it for the device path (mn_select, MPIR_Allreduce_two_level_MV2,
 // MPIR_Reduce_two_level_helper_MV2, the flat algorithms over every rank).  MN_FLAT: `p` holds this
 // rank's programs over the job's ranks (forced: the plan_allreduce / plan_reduce argument that
 // reproduces any rank's; for the ring, elements [0, U) take `p` and [U, count) `rem`, counted from

@@ -240,7 +240,7 @@ int run_copies(const std::vector<Copy> &cp) {
         auto t0 = std::chrono::steady_clock::now();
         double next_us = 200.0;
         // a word raised by a copy kernel whose block groups ran on several XCDs (device_util.h
-        // block_done): done once the stream is, as for the collectives (coll.cpp settle_split)
+        // block_done): done once the stream is, as for the collectives (call.cpp settle_split)
         auto settle = [&]() {
             static uint64_t seen = 0;
             const uint64_t s = __atomic_load_n(g_pdone.flag + 1, __ATOMIC_ACQUIRE);

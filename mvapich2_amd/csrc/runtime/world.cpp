@@ -819,7 +819,7 @@ int world_init() {
             // rank per GPU, or MV2AMD_PIPE_AUTOTUNE=1) and no limit is set, the slots hold up to
             // 1 MiB so that the probe can find a crossover above the 256 KiB default: on xGMI a
             // one-shot call of 512 KiB - 1 MiB moves (n-1) x size per rank in one flag exchange
-            // against the pipelined kernel's two (coll.cpp oneshot_autotune)
+            // against the pipelined kernel's two (coll_init.cpp oneshot_autotune)
             {
                 const long at = env_long("MV2AMD_PIPE_AUTOTUNE", -1);
                 const bool tunes = at == 1 || (at < 0 && w.nshare == 1);

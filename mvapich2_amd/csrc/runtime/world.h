@@ -135,7 +135,7 @@ struct World {
     EpochRec epoch_log[8] = {};
     unsigned epoch_pos = 0;
 
-    // graph lane (HIP graph capture of stream-ordered allreduce, coll.cpp): its own signal page,
+    // graph lane (HIP graph capture of stream-ordered allreduce, coll_node.cpp): its own signal page,
     // one-shot arena and pipeline arenas, with the sequence numbers kept on the device (DevSeq)
     bool graph_lane = false;
     bool graph = false;  // the current call is being captured into a graph
@@ -183,7 +183,7 @@ struct World {
     // hipFree that synchronises the device); stays flat once the scratch caches are warm
     uint64_t call_allocs = 0;
     uint64_t pool_trims = 0;  // idle pool blocks returned to HIP above MV2AMD_POOL_IDLE_MAX (world.cpp pool_put)
-    // completion-word events (coll.cpp wait_done), reported by mv2h_get_info and both bench lines:
+    // completion-word events (call.cpp wait_done), reported by mv2h_get_info and both bench lines:
     // the stream was consulted (the word unseen 200 us after the launch); the word was seen only
     // after the stream reported the kernel finished; the kernel had ended without raising it; the
     // kernel raised it marked "groups split over XCDs" (device_util.h block_done), so the host
@@ -257,13 +257,13 @@ void *pool_get(size_t bytes);
 void pool_put(void *p);  // back to the pool (the device work using it has completed)
 bool coll_context_poisoned();  // runtime/p2p.cpp: an abandoned collective request is still in flight
 unsigned long long p2p_unexpected_matched();  // runtime/p2p.cpp: unexpected messages later taken by a receive
-// runtime/coll.cpp: across nodes, the most ranks (and node leaders) a flat algorithm runs as
+// runtime/coll_mn.cpp: across nodes, the most ranks (and node leaders) a flat algorithm runs as
 // per-element programs; above it, its message schedule (MV2AMD_MN_PROG_MAX, default kMaxRanks)
 int mn_prog_max();
-int coll_selftest();  // coll.cpp: init-time check of the cross-GPU publish protocol
-void pipe_tiling_for(size_t seg_bytes, int *grid, size_t *tsub);  // coll.cpp: a segment's grid and bytes per round
-int pipe_autotune();  // coll.cpp: init-time choice of the pipelined kernels' tiling
-void host_prof_report();  // coll.cpp: MV2AMD_HOST_PROFILE summary
+int coll_selftest();  // coll_init.cpp: init-time check of the cross-GPU publish protocol
+void pipe_tiling_for(size_t seg_bytes, int *grid, size_t *tsub);  // coll_node.cpp: a segment's grid and bytes per round
+int pipe_autotune();  // coll_init.cpp: init-time choice of the pipelined kernels' tiling
+void host_prof_report();  // call.cpp: MV2AMD_HOST_PROFILE summary
 // The library's own messages on the node's point-to-point channels (the steps of the multi-node
 // collectives) carry tags below kCollTagBase: the collective context of MPICH's comm (context_id +
 // MPID_CONTEXT_INTRA_COLL), so no application receive, MPI_ANY_TAG included, can match them.

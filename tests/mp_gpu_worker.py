@@ -618,6 +618,59 @@ def upload_churn(L, case, rank, n):
     return np.array([fail, i + 1, wrong], dtype=np.int64)
 
 
+class Operand:
+    """Operand memory the library may have to stage: pageable host memory ("host"), device memory
+    4 bytes past a 16-byte boundary ("dev4"), or aligned device memory ("dev")."""
+
+    def __init__(self, nbytes, where):
+        self.host = np.zeros(nbytes, dtype=np.uint8) if where == "host" else None
+        self.dev = None if where == "host" else m.DeviceBuffer(nbytes + 16)
+        self.off = 4 if where == "dev4" else 0
+        self.ptr = self.host.ctypes.data if where == "host" else self.dev.ptr + self.off
+
+    def put(self, arr, at=0):
+        b = np.ascontiguousarray(arr).view(np.uint8).ravel()
+        if self.host is not None:
+            self.host[at:at + b.size] = b
+        else:
+            self.dev.upload(b, self.off + at)
+
+    def get(self, nbytes):
+        if self.host is not None:
+            return self.host[:nbytes].copy()
+        return self.dev.download(np.uint8, count=nbytes, offset=self.off)
+
+
+def staged(L, case, rank, n):
+    """One blocking MPI_INT MPI_SUM collective (case["coll"]) with its send and receive operands
+    where case["send"] / case["recv"] say (Operand; send "in_place": MPI_IN_PLACE, and in a reduce
+    the other ranks' operands where the root's recvbuf is).  count 0: 3 elements more than the
+    one-shot limit the library reports, i.e. the smallest pipelined call.  Returns the result bytes
+    (reduce: the root's, an empty array elsewhere) and saves the count it ran with."""
+    count = case["count"] or m.info("oneshot_max") // 4 + 3
+    np.save(os.path.join(sys.argv[2], f"{case['id']}_count_r{rank}.npy"), np.array([count], dtype=np.int64))
+    I, SUM, coll, root, nb = TYPES["MPI_INT"][0], OPS["MPI_SUM"], case["coll"], case.get("root", 0), count * 4
+    x = inputs(dict(case, count=count), rank)
+    out_bytes = nb * n if coll == "allgather" else nb
+    rb = Operand(out_bytes, case["recv"])
+    rb.put(np.full(out_bytes, 0xA5, dtype=np.uint8))
+    if case["send"] == "in_place" and (coll != "reduce" or rank == root):
+        rb.put(x, rank * nb if coll == "allgather" else 0)
+        sp = P(-1 & 0xFFFFFFFFFFFFFFFF)
+    else:
+        sb = Operand(nb, case["recv"] if case["send"] == "in_place" else case["send"])
+        sb.put(x)
+        sp = P(sb.ptr)
+    if coll == "allreduce":
+        rc = L.MPI_Allreduce(sp, P(rb.ptr), count, I, SUM, WORLD)
+    elif coll == "reduce":
+        rc = L.MPI_Reduce(sp, P(rb.ptr), count, I, SUM, root, WORLD)
+    else:
+        rc = L.MPI_Allgather(sp, count, I, P(rb.ptr), count, I, WORLD)
+    assert rc == 0, (case["id"], rc)
+    return rb.get(out_bytes if coll != "reduce" or rank == root else 0)
+
+
 def main():
     spec = json.load(open(sys.argv[1]))
     out = sys.argv[2]
@@ -876,6 +929,8 @@ def main():
             res = arg_checks(L, rank, n)
         elif k == "soak":
             res = soak(L, case, rank, n)
+        elif k == "staged":  # host and misaligned operands: the staging of the node collectives
+            res = staged(L, case, rank, n)
         elif k == "upload_churn":  # diagnosis (tools/runs/run_r06an.sh): pageable uploads between calls
             res = upload_churn(L, case, rank, n)
         elif k == "peer_absent":  # a collective one rank never enters: the others' device wait runs out

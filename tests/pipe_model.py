@@ -1,5 +1,5 @@
 """Host model of the pipelined push collectives (k_pipe, csrc/coll/pipe.h and
-the geometry in csrc/runtime/coll.cpp): segment layout, round / workgroup
+the geometry in csrc/runtime/coll_node.cpp): segment layout, round / workgroup
 ranges, arena slots [parity][source], and the per-element reduction order
 (LINEAR / BUTTERFLY with reduce-scatter owner bitrev(block)).  Arithmetic is
 delegated to the oracle's op loop, so the model checks the decomposition and
@@ -15,7 +15,7 @@ PIPE_MIN_SUB = 16 << 10
 
 
 def pipe_geom(maxlen, cus=256, nshare=1, pipe_grid=PIPE_MAX_GRID, pipe_sub=PIPE_MAX_SUB):
-    """coll.cpp pipe_geom(): (grid, tsub, tseg, nrounds)."""
+    """coll_node.cpp pipe_geom(): (grid, tsub, tseg, nrounds)."""
     cap = min(PIPE_MAX_GRID, max(1, cus // max(1, nshare)), max(1, pipe_grid))
     g = min(cap, max(1, -(-maxlen // PIPE_MIN_SUB)))
     tsub = -(-maxlen // g)
@@ -26,7 +26,7 @@ def pipe_geom(maxlen, cus=256, nshare=1, pipe_grid=PIPE_MAX_GRID, pipe_sub=PIPE_
 
 
 def even_segments(nbytes, n):
-    """coll.cpp even_segments(): [(offset, length)] per rank, 16-byte aligned."""
+    """coll_node.cpp even_segments(): [(offset, length)] per rank, 16-byte aligned."""
     seg = ((-(-nbytes // n)) + 15) & ~15
     out = []
     for j in range(n):
@@ -45,7 +45,7 @@ def tree_params(n, count, size):
 
 
 def ring_segments(count, ext, n):
-    """coll.cpp AR_RING: segment j = ring chunk j of count/n elements (count % n == 0)."""
+    """coll_node.cpp AR_RING: segment j = ring chunk j of count/n elements (count % n == 0)."""
     cb = (count // n) * ext
     return [(j * cb, cb) for j in range(n)]
 

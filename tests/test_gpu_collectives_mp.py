@@ -56,7 +56,7 @@ def run_workers(n, cases, tmp_path, timeout=100, extra_env=None, ppn=None, expec
         boot = {"MV2AMD_BOOT_ADDR": "127.0.0.1", "MV2AMD_BOOT_PORT": str(so.getsockname()[1]),
                 "MV2AMD_NSHARE": str(n),  # every emulated node's ranks share the one GPU
                 # the default 30 s: a device wait that runs out prints the epoch it waited for and
-                # the flags it saw (coll.cpp check_err_word), so a stall names itself
+                # the flags it saw (call.cpp check_err_word), so a stall names itself
                 "MV2AMD_TIMEOUT_S": "30"}
         timeout = max(timeout, 240)
         so.close()
@@ -291,6 +291,45 @@ def test_collectives_multiprocess(n, geom, tmp_path, golden):
                 assert np.array_equal(got[:, :4], src[:, :4]), (cid, r)
                 if r != case["root"]:
                     assert np.all(got[:, 4:] == -1.0), "gap bytes of a vector type must not be written"
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("n", [2, 3])
+def test_staged_operands(n, tmp_path):
+    """Operands the node collectives have to stage (coll_node.cpp stage_in / device_operand, the
+    allgather's packed result): a host send buffer, a device send buffer 4 bytes past a 16-byte
+    boundary, a host or such a misaligned receive buffer, and MPI_IN_PLACE on both, for
+    MPI_Allreduce, MPI_Reduce (root and non-roots) and MPI_Allgather, each at 272 bytes (the
+    one-shot kernels) and 12 bytes above the one-shot limit the library reports (the pipelined
+    ones).  MPI_INT MPI_SUM, bit for bit against the oracle."""
+    cases = []
+    for coll in ("allreduce", "reduce", "allgather"):
+        for count in (68, 0):  # 0: mp_gpu_worker.staged takes oneshot_max / 4 + 3
+            for send, recv in (("host", "dev"), ("dev4", "dev"), ("dev", "host"), ("dev", "dev4"),
+                               ("in_place", "host"), ("in_place", "dev4")):
+                cases.append({"id": f"st{len(cases)}", "kind": "staged", "coll": coll, "send": send, "recv": recv,
+                              "count": count, "type": "MPI_INT", "op": "MPI_SUM", "seed": 900 + len(cases),
+                              "root": n - 1})
+    res = run_workers(n, cases, tmp_path)
+    for case in cases:
+        cid, coll, root = case["id"], case["coll"], case["root"]
+        counts = [int(np.load(tmp_path / "out" / f"{cid}_count_r{r}.npy")[0]) for r in range(n)]
+        count = counts[0]
+        assert counts == [count] * n and (case["count"] in (0, count)) and count * 4 >= 272
+        sends = [as_bytes(inputs(dict(case, count=count), r)).copy() for r in range(n)]
+        what = f"{cid} {coll} count={count} send={case['send']} recv={case['recv']}"
+        if coll == "allreduce":
+            want = oracle.allreduce_ref(sends, count, TYPES["MPI_INT"][0], OPS["MPI_SUM"],
+                                        in_place=case["send"] == "in_place")
+            for r in range(n):
+                assert_bytes_equal(res(cid, r), want[r], "MPI_INT", count, f"{what} rank {r}")
+        elif coll == "reduce":
+            want = oracle.reduce_ref(sends, count, TYPES["MPI_INT"][0], OPS["MPI_SUM"], root)
+            assert_bytes_equal(res(cid, root), want, "MPI_INT", count, what)
+        else:
+            want = np.concatenate(sends)
+            for r in range(n):
+                assert np.array_equal(res(cid, r), want), (what, r)
 
 
 def ufn(inp, io):
@@ -530,7 +569,7 @@ def test_mpit_counters_follow_the_selection(tmp_path):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_pipe_autotune_agrees_and_keeps_results(n, tmp_path):
-    """MPI_Init's tiling autotune (coll.cpp pipe_autotune), forced on the shared GPU with a
+    """MPI_Init's tiling autotune (coll_init.cpp pipe_autotune), forced on the shared GPU with a
     16 MiB probe: every rank adopts the same grid and bytes per workgroup (workgroup b of every
     rank pairs with workgroup b), and the calls after it stay bit-exact with the oracle (the
     tiling never changes the reduction order)."""
@@ -696,9 +735,9 @@ def test_random_sequence_across_nodes(n, ppn, seed0, prog_max, tmp_path):
 
 PROTOCOL_VARIANTS = [
     # the full system-scope release MPI_Init's self-test falls back to when the light release fails
-    # on a topology (coll.cpp coll_selftest) — never taken on a shared GPU by itself
+    # on a topology (coll_init.cpp coll_selftest) — never taken on a shared GPU by itself
     {"MV2AMD_LIGHT_RELEASE": "0"},
-    # tilings the init-time autotune can adopt over xGMI (coll.cpp kGrid / kSub), with the
+    # tilings the init-time autotune can adopt over xGMI (coll_init.cpp kGrid / kSub), with the
     # one-shot path narrowed so the pipelined kernel carries the small sizes too
     {"MV2AMD_PIPE_GRID": "64", "MV2AMD_PIPE_SUB": str(512 << 10)},
     {"MV2AMD_PIPE_GRID": "256", "MV2AMD_PIPE_SUB": str(16 << 10), "MV2AMD_ONESHOT_MAX": str(16 << 10)},
@@ -975,7 +1014,7 @@ def test_absent_peer_is_reported_not_hung(tmp_path):
     MV2AMD_TIMEOUT_S, its MPI_Allreduce returns MPI_ERR_OTHER (MPI_ERRORS_RETURN) instead of hanging,
     and the report names what was awaited -- the epoch, the flags seen, the launch that waited
     (call number and epochs), the waited slot as a copy re-reads it from memory (the absent rank's
-    older than the epoch), and where the absent rank's host is (coll.cpp check_err_word).  Both
+    older than the epoch), and where the absent rank's host is (call.cpp check_err_word).  Both
     ranks then finalize normally."""
     # the host barriers share the timeout: the absent rank reaches MPI_Finalize's after 4.5 s, once the
     # other rank's 3 s device wait has been reported, and well within that rank's 3 s barrier wait

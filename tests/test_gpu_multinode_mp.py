@@ -118,7 +118,7 @@ def table_entry(ppn, n, nbytes, knobs=None):
 
 
 def expected_allreduce(sends, count, t, op, ppn, in_place=False):
-    """per-rank results of MPI_Allreduce across nodes, by the selection coll.cpp mn_allreduce
+    """per-rank results of MPI_Allreduce across nodes, by the selection coll_mn.cpp mn_allreduce
     restates: flat ring from 2 MiB (remainder, IN_PLACE and count < n: the wrapper's flat pt2pt_rs
     over every rank), the small-message shortcuts' two-level order up to 2 KiB, then the tables'
     flat pt2pt_rs / pt2pt_rd or two-level entry"""
@@ -434,7 +434,7 @@ def _ufn(a, b):
 
 
 def user_allreduce_across(xs, commute, count, ppn):
-    """MPI_Allreduce with a user op across nodes (coll.cpp mn_host_schedule): non-commutative ->
+    """MPI_Allreduce with a user op across nodes (coll_mn.cpp mn_host_schedule): non-commutative ->
     recursive doubling over every rank; commutative -> mn_select's schedule: the topology-aware
     shortcut up to 2 KiB (node tree, leaders' recursive doubling), a 2-ppn two-level entry
     (reduce_shmem + recursive doubling), else the tables' flat pt2pt_rs, which a user op turns into
@@ -462,7 +462,7 @@ def user_allreduce_across(xs, commute, count, ppn):
 
 
 def user_reduce_across(xs, commute, count, ppn, root):
-    """MPI_Reduce with a user op across nodes (coll.cpp mn_host_schedule): non-commutative -> the
+    """MPI_Reduce with a user op across nodes (coll_mn.cpp mn_host_schedule): non-commutative -> the
     flat binomial; commutative -> the device path's selection (expected_reduce), with a user op's
     flat redscat_gather falling back to binomial (it needs a builtin op, reduce_osu.c:2645-2652) while
     the two-level helper's leaders run the table's function as it is (:2315)"""
@@ -631,7 +631,7 @@ def test_more_than_eight_ranks_across_nodes(n, ppn, tmp_path):
     """What jobs of more than 8 ranks run, on at most 8 processes (more must not share the one GPU,
     DESIGN.md §5 "Ranks per GPU"): with the programs' limit lowered to 4 (MV2AMD_MN_PROG_MAX) the
     flat pt2pt_rs / pt2pt_rd the tables name over every rank, and the ring wrapper's pt2pt_rs
-    remainder, run as the reference's message schedule over the point-to-point channels (coll.cpp
+    remainder, run as the reference's message schedule over the point-to-point channels (coll_mn.cpp
     sched_allreduce, RankChannels); the small-message shortcut's recursive doubling over more node
     leaders than the limit (8x1: LeaderLinks); MPI_Reduce_scatter's schedules over every rank
     (sched_rs_halving / _pairwise / _ring); the nonblocking Iallreduce / Ireduce schedules flat over

@@ -201,7 +201,7 @@ def test_completion_word_fallbacks_are_counted():
     """A missed completion word is visible: a Reduce_local launched with its word
     withheld completes through the stream fallback with the right bytes and counts done_queried and
     done_missed; a word marked as raised by a kernel whose block groups ran on several XCDs
-    completes by stream synchronisation and counts done_xcd_split (runtime/coll.cpp wait_done,
+    completes by stream synchronisation and counts done_xcd_split (runtime/call.cpp wait_done,
     settle_split; device_util.h block_done)."""
     L = m.lib()
     n = (1 << 20) + 5

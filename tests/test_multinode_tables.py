@@ -82,7 +82,7 @@ E_UNSUPPORTED = 44
                                        (16, 128), (8, 128), (16, 1024)])
 def test_every_builtin_route_is_supported(ppn, gsize):
     """above 64 ranks (no rank mesh) a flat algorithm's message schedule cannot
-    run; the multi-node dispatch (coll.cpp mn_*_route) must then take the two-level stand-in, never
+    run; the multi-node dispatch (coll_mn.cpp mn_*_route) must then take the two-level stand-in, never
     refuse a builtin op.  Every size from 4 B to 1 GiB, blocking and nonblocking, IN_PLACE or not."""
     L = m.lib()
     rem = ctypes.c_int()
@@ -145,7 +145,7 @@ def test_reduce_table_reads_duplicate_first_entries_by_index():
 
 
 def test_prog_max_knob_moves_flat_calls_onto_the_message_schedules():
-    """MV2AMD_MN_PROG_MAX (coll.cpp mn_prog_max): with it at 4, an 8-rank job takes the message
+    """MV2AMD_MN_PROG_MAX (world.cpp mn_prog_max): with it at 4, an 8-rank job takes the message
     schedules that jobs above 8 ranks take, so the GPU tests cover them on 8 processes (DESIGN.md §5
     "Ranks per GPU"); unset, 8 ranks run as programs.  Read once per process: a child process."""
     import subprocess
