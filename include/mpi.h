@@ -295,6 +295,11 @@ int MPI_Exscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datat
                MPI_Comm comm);
 int MPI_Allgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
                   int recvcount, MPI_Datatype recvtype, MPI_Comm comm);
+int MPI_Alltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
+                 int recvcount, MPI_Datatype recvtype, MPI_Comm comm);
+int MPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[],
+                  MPI_Datatype sendtype, void *recvbuf, const int recvcounts[], const int rdispls[],
+                  MPI_Datatype recvtype, MPI_Comm comm);
 int MPI_Bcast(void *buffer, int count, MPI_Datatype datatype, int root, MPI_Comm comm);
 
 /* ---- nonblocking collectives + request completion (MPI-3.1 5.12, 3.7.3) ---- */
@@ -313,6 +318,11 @@ int MPI_Iexscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype data
                 MPI_Comm comm, MPI_Request *request);
 int MPI_Iallgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
                    int recvcount, MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request);
+int MPI_Ialltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
+                  int recvcount, MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request);
+int MPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[],
+                   MPI_Datatype sendtype, void *recvbuf, const int recvcounts[], const int rdispls[],
+                   MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request);
 int MPI_Ibcast(void *buffer, int count, MPI_Datatype datatype, int root, MPI_Comm comm,
                MPI_Request *request);
 int MPI_Ibarrier(MPI_Comm comm, MPI_Request *request);
@@ -337,6 +347,9 @@ int MPIX_Reduce_scatter_enqueue(const void *sendbuf, void *recvbuf, const int re
 int MPIX_Allgather_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sendtype,
                            void *recvbuf, int recvcount, MPI_Datatype recvtype, MPI_Comm comm,
                            void *stream);
+int MPIX_Alltoall_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sendtype,
+                          void *recvbuf, int recvcount, MPI_Datatype recvtype, MPI_Comm comm,
+                          void *stream);
 int MPIX_Bcast_enqueue(void *buffer, int count, MPI_Datatype datatype, int root, MPI_Comm comm,
                        void *stream);
 int MPIX_Enqueue_check(MPI_Comm comm);
@@ -428,6 +441,11 @@ int PMPI_Iexscan(const void *sendbuf, void *recvbuf, int count, MPI_Datatype dat
                  MPI_Comm comm, MPI_Request *request);
 int PMPI_Allgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
                    int recvcount, MPI_Datatype recvtype, MPI_Comm comm);
+int PMPI_Alltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
+                 int recvcount, MPI_Datatype recvtype, MPI_Comm comm);
+int PMPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[],
+                  MPI_Datatype sendtype, void *recvbuf, const int recvcounts[], const int rdispls[],
+                  MPI_Datatype recvtype, MPI_Comm comm);
 int PMPI_Bcast(void *buffer, int count, MPI_Datatype datatype, int root, MPI_Comm comm);
 int PMPI_Iallreduce(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype,
                    MPI_Op op, MPI_Comm comm, MPI_Request *request);
@@ -440,6 +458,11 @@ int PMPI_Ireduce_scatter_block(const void *sendbuf, void *recvbuf, int recvcount
                               MPI_Request *request);
 int PMPI_Iallgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
                    int recvcount, MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request);
+int PMPI_Ialltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf,
+                  int recvcount, MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request);
+int PMPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[],
+                   MPI_Datatype sendtype, void *recvbuf, const int recvcounts[], const int rdispls[],
+                   MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request);
 int PMPIX_Allreduce_enqueue(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype,
                             MPI_Op op, MPI_Comm comm, void *stream);
 int PMPIX_Reduce_enqueue(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype,
@@ -449,6 +472,9 @@ int PMPIX_Reduce_scatter_enqueue(const void *sendbuf, void *recvbuf, const int r
 int PMPIX_Allgather_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sendtype,
                             void *recvbuf, int recvcount, MPI_Datatype recvtype, MPI_Comm comm,
                             void *stream);
+int PMPIX_Alltoall_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sendtype,
+                          void *recvbuf, int recvcount, MPI_Datatype recvtype, MPI_Comm comm,
+                          void *stream);
 int PMPIX_Bcast_enqueue(void *buffer, int count, MPI_Datatype datatype, int root, MPI_Comm comm,
                         void *stream);
 int PMPIX_Enqueue_check(MPI_Comm comm);

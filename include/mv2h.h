@@ -80,6 +80,24 @@ int mv2h_scan(const void *sendbuf, void *recvbuf, size_t count, int dtype, int o
 int mv2h_exscan(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);
 int mv2h_allgather(const void *sendbuf, void *recvbuf, size_t bytes_per_rank, void *stream);
 int mv2h_bcast(void *buffer, size_t bytes, int root, void *stream);
+/* MPI_Alltoall / MPI_Alltoallv on one node (MPIR_Alltoall_MV2 alltoall_osu.c:1611-1724, whose device
+ * path is MPIR_Alltoall_CUDA_intra_MV2 alltoall_cuda_osu.c:66; MPIR_Alltoallv_MV2 alltoallv_osu.c).
+ * Block j of sendbuf goes to rank j; rank j's block lands at block j of recvbuf.  sendbuf ==
+ * (void *)-1 (MPI_IN_PLACE): the blocks are read from recvbuf (Alltoallv: sbytes / soffs ignored).
+ * Alltoallv takes byte counts and byte offsets; only bytes of receive blocks are written; a pair
+ * whose send and receive lengths differ returns MPI_ERR_TRUNCATE's class on every rank before any
+ * device work.  Its ranks meet on the host inside the call, so it has no _enqueue form.  A job
+ * over several nodes is refused with MPI_ERR_OTHER's class before any device work. */
+int mv2h_alltoall(const void *sendbuf, void *recvbuf, size_t bytes_per_block, void *stream);
+int mv2h_alltoallv(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf,
+                   const size_t *rbytes, const size_t *roffs, void *stream);
+/* Test hook: the plan every rank derives for one MPI_Alltoallv from the whole n x n matrix
+ * (slen[i * n + j]: bytes rank i sends rank j; rlen[i * n + j]: bytes rank i expects from rank j;
+ * aligned16[i]: every offset of rank i is a multiple of 16) and the node's shared limits.  *path:
+ * 0 nothing to move, 1 one-shot vectors, 2 one-shot byte-wise, 3 pipelined.  Returns
+ * MPI_ERR_TRUNCATE's class when a pair's two lengths differ. */
+int mv2h_alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned char *aligned16, int *path,
+                        int *grid, int *nrounds, size_t *maxlen);
 int mv2h_barrier(void);
 
 /* ---- stream-ordered collectives (SURVEY §8(f) rank 3 "stream-ordered variants") ----
@@ -99,6 +117,7 @@ int mv2h_reduce_enqueue(const void *sendbuf, void *recvbuf, size_t count, int dt
 int mv2h_reduce_scatter_enqueue(const void *sendbuf, void *recvbuf, const size_t *recvcounts,
                                 int dtype, int op, void *stream);
 int mv2h_allgather_enqueue(const void *sendbuf, void *recvbuf, size_t bytes_per_rank, void *stream);
+int mv2h_alltoall_enqueue(const void *sendbuf, void *recvbuf, size_t bytes_per_block, void *stream);
 int mv2h_bcast_enqueue(void *buffer, size_t bytes, int root, void *stream);
 int mv2h_copy_enqueue(void *dst, const void *src, size_t bytes, void *stream);
 int mv2h_enqueue_check(void);
@@ -281,6 +300,8 @@ int mv2h_set_tuning(const char *key, long value);
  * autotune), "tune_n" and per candidate k "tune_grid_<k>", "tune_sub_<k>", "tune_us_<k>" (max over ranks),
  * "init_us" / "hip_init_us" / "code_load_us" / "selftest_us" / "autotune_us" (this rank's MPI_Init
  * wall time and its parts), "selftest_calls" (collective calls MPI_Init's self-test checked),
+ * "a2a_oneshot_vec" / "a2a_oneshot_bytes" / "a2a_pipe" / "a2a_pipe_shift" (all-to-all calls by path: one-shot by vectors, one-shot byte by
+ * byte, pipelined, and those of the pipelined ones whose gather shifted a block),
  * "call_allocs" (device allocations made inside MPI calls: scratch growth, pooled temporaries),
  * "hw_queues_set" (GPU_MAX_HW_QUEUES set before HIP started; negative: wanted, but HIP was already
  * running), "rl_tiny_max" / "rl_grid" / "max_grid" (the launch tunings of the same names as they stand:

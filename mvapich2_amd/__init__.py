@@ -57,6 +57,12 @@ def lib():
         "mv2h_reduce_scatter": ([c_vp, c_vp, ctypes.POINTER(c_sz), c_int, c_int, c_vp], c_int),
         "mv2h_allgather": ([c_vp, c_vp, c_sz, c_vp], c_int),
         "mv2h_bcast": ([c_vp, c_sz, c_int, c_vp], c_int),
+        "mv2h_alltoall": ([c_vp, c_vp, c_sz, c_vp], c_int),
+        "mv2h_alltoall_enqueue": ([c_vp, c_vp, c_sz, c_vp], c_int),
+        "mv2h_alltoallv": ([c_vp, ctypes.POINTER(c_sz), ctypes.POINTER(c_sz), c_vp, ctypes.POINTER(c_sz),
+                            ctypes.POINTER(c_sz), c_vp], c_int),
+        "mv2h_alltoallv_plan": ([c_int, ctypes.POINTER(c_sz), ctypes.POINTER(c_sz), ctypes.c_char_p, ctypes.POINTER(c_int),
+                                 ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_sz)], c_int),
         "mv2h_barrier": ([], c_int),
         "mv2h_pack_strided": ([c_vp, c_vp, c_sz, c_sz, c_sz, c_vp], c_int),
         "mv2h_unpack_strided": ([c_vp, c_vp, c_sz, c_sz, c_sz, c_vp], c_int),
@@ -101,6 +107,9 @@ def lib():
         "MPI_Iexscan": ([c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Allgather": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int], c_int),
         "MPI_Bcast": ([c_vp, c_int, c_int, c_int, c_int], c_int),
+        "MPI_Alltoall": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int], c_int),
+        "MPI_Alltoallv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, ctypes.POINTER(c_int),
+                           ctypes.POINTER(c_int), c_int, c_int], c_int),
         "MPI_Op_create": ([c_vp, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Op_free": ([ctypes.POINTER(c_int)], c_int),
         "MPI_Type_vector": ([c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
@@ -132,6 +141,9 @@ def lib():
         "MPI_Ireduce_scatter_block": ([c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Iallgather": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Ibcast": ([c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
+        "MPI_Ialltoall": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
+        "MPI_Ialltoallv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, ctypes.POINTER(c_int),
+                            ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Ibarrier": ([c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Wait": ([ctypes.POINTER(c_int), c_vp], c_int),
         "MPI_Test": ([ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp], c_int),
@@ -148,6 +160,7 @@ def lib():
         "MPIX_Reduce_scatter_enqueue": ([c_vp, c_vp, ctypes.POINTER(c_int), c_int, c_int, c_int, c_vp], c_int),
         "MPIX_Allgather_enqueue": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp], c_int),
         "MPIX_Bcast_enqueue": ([c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),
+        "MPIX_Alltoall_enqueue": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp], c_int),
         "MPIX_Enqueue_check": ([c_int], c_int),
     }
     for name, (args, res) in sigs.items():
@@ -217,7 +230,41 @@ def reduce_local(inbuf, inoutbuf, count, type_name, op_name, offset_in=0, offset
                                    TYPES[type_name][0], OPS[op_name], None)
 
 
-__all__ = ["lib", "check", "DeviceBuffer", "MPIError", "reduce_local", "np_dtype", "consts", "OPS", "TYPES"]
+def alltoall(sendbuf, recvbuf, bytes_per_block, stream=None):
+    """MPI_Alltoall of bytes_per_block bytes per pair on device buffers (mv2h_alltoall);
+    sendbuf=None: MPI_IN_PLACE."""
+    return lib().mv2h_alltoall(sendbuf.ptr if sendbuf is not None else ctypes.c_void_p(-1), recvbuf.ptr,
+                               bytes_per_block, stream)
+
+
+def alltoallv(sendbuf, sbytes, soffs, recvbuf, rbytes, roffs):
+    """MPI_Alltoallv in bytes on device buffers (mv2h_alltoallv); sendbuf=None: MPI_IN_PLACE."""
+    n = len(rbytes)
+    arr = lambda v: (ctypes.c_size_t * n)(*v) if v is not None else None  # noqa: E731
+    return lib().mv2h_alltoallv(sendbuf.ptr if sendbuf is not None else ctypes.c_void_p(-1), arr(sbytes), arr(soffs),
+                                recvbuf.ptr, arr(rbytes), arr(roffs), None)
+
+
+A2A_PATHS = {0: "none", 1: "oneshot_vec", 2: "oneshot_bytes", 3: "pipe"}
+
+
+def alltoallv_plan(slen, rlen=None, aligned16=None):
+    """(rc, path, grid, nrounds, maxlen) every rank derives for one MPI_Alltoallv from the n x n
+    matrix slen[i][j] = bytes rank i sends rank j (rlen[i][j]: bytes rank i expects from rank j;
+    default: the transpose, i.e. a matching call)."""
+    n = len(slen)
+    if rlen is None:
+        rlen = [[slen[j][i] for j in range(n)] for i in range(n)]
+    flat = lambda m: (ctypes.c_size_t * (n * n))(*[v for row in m for v in row])  # noqa: E731
+    al = bytes([1] * n if aligned16 is None else [int(bool(a)) for a in aligned16])
+    path, grid, rounds, maxlen = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    rc = lib().mv2h_alltoallv_plan(n, flat(slen), flat(rlen), al, ctypes.byref(path), ctypes.byref(grid),
+                                   ctypes.byref(rounds), ctypes.byref(maxlen))
+    return rc, A2A_PATHS[path.value], grid.value, rounds.value, maxlen.value
+
+
+__all__ = ["lib", "check", "DeviceBuffer", "MPIError", "reduce_local", "alltoall", "alltoallv", "alltoallv_plan",
+           "np_dtype", "consts", "OPS", "TYPES"]
 
 
 # ---- reduction-order plans (host only) ----

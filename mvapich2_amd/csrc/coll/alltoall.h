@@ -1,0 +1,43 @@
+// alltoall.h — host-side launch interface of the all-to-all kernels (coll/alltoall.hip).
+#pragma once
+#include "kernels.h"
+
+namespace mv2 {
+
+// One all-to-all over this node's ranks (MPI_Alltoall: every pair the same length; MPI_Alltoallv:
+// a length per pair).  Rank me sends slen[j] bytes at send + soff[j] to rank j and receives
+// rlen[j] bytes from rank j at recv + roff[j]; slen[j] on rank me equals rlen[me] on rank j.
+// send and recv are 16-byte aligned (the runtime stages anything else); the offsets are not.
+struct A2AArgs {
+    int n, me;
+    const char *send;
+    char *recv;
+    size_t soff[kMaxRanks], slen[kMaxRanks];
+    size_t roff[kMaxRanks], rlen[kMaxRanks];
+    // smis[j]: rank j's (soff[me] & 15), the misalignment its block arrives with (pipelined kernel)
+    uint32_t smis[kMaxRanks];
+    // one-shot kernel: nvec = 16-byte vectors of the longest pair, partitioned over the workgroups
+    // (every offset and length is then a multiple of 16); 0 = byte by byte through workgroup 0
+    PeerTableW arena_peer;  // peers' one-shot arena (this call's half); my slot at + me * slot_bytes
+    const char *arena_own;  // my arena (same half); rank j's slot at + j * slot_bytes
+    size_t nvec, slot_bytes, half;
+    // pipelined kernel (k_pipe's tiling, slot parities and flags; the AG region only)
+    PeerTableW ag_peer;
+    size_t tseg, tsub;
+    uint64_t round0;
+    int nrounds;
+    int rnt;  // 1: non-temporal stores into peers' arenas
+    SigTable sig_peer;
+    uint64_t *sig_own;
+    uint64_t epoch0;  // one-shot: the call's epoch; pipelined: round k uses epoch0 + 2k
+    int light;
+    int *err;
+    uint64_t timeout;
+    Done done;
+    DevSeq *dseq;  // graph lane
+};
+
+int launch_oneshot_a2a(const A2AArgs &a, const LaunchCfg &cfg);
+int launch_pipe_a2a(const A2AArgs &a, const LaunchCfg &cfg);
+
+}  // namespace mv2

@@ -791,6 +791,125 @@ int PMPI_Allgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, vo
 int MPI_Allgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
                   MPI_Datatype recvtype, MPI_Comm comm) WEAK(MPI_Allgather);
 
+// ---------------------------------------------------------------------------
+// MPI_Alltoall / MPI_Alltoallv (alltoall.c:650-713, alltoallv.c:520-594 for the checks).
+// MPI_IN_PLACE is the send buffer only; with it the send count and type (sendcounts / sdispls)
+// are ignored and the blocks are read from recvbuf.
+// ---------------------------------------------------------------------------
+static int alltoall_checks(const void *sendbuf, int sendcount, MPI_Datatype sendtype, const void *recvbuf,
+                           int recvcount, MPI_Datatype recvtype, MPI_Comm comm) {
+    if (!g_initialized || g_finalized) return MPI_ERR_OTHER;
+    if (comm_index(comm) < 0) return MPI_ERR_COMM;
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    if (recvcount < 0 || (!in_place && sendcount < 0)) return MPI_ERR_COUNT;
+    if (!dtype_valid(recvtype) || (!in_place && !dtype_valid(sendtype))) return MPI_ERR_TYPE;
+    if (!dtype_committed(recvtype) || (!in_place && !dtype_committed(sendtype))) return MPI_ERR_TYPE;
+    if (!in_place && null_userbuf(sendbuf, sendcount, sendtype)) return MPI_ERR_BUFFER;
+    if (inplace_buf(recvbuf, recvcount) || null_userbuf(recvbuf, recvcount, recvtype)) return MPI_ERR_BUFFER;
+    if (!in_place && sendcount != 0 && recvcount != 0 && sendbuf == recvbuf) return MPI_ERR_BUFFER;  // alltoall.c:690-695
+    return MPI_SUCCESS;
+}
+
+// Alltoall with a non-contiguous type on either side, the way of allgather_derived: pack the n
+// send blocks on the device (block j is elements [j * sendcount, (j + 1) * sendcount), so the n
+// blocks are n * sendcount consecutive elements), exchange the packed bytes, unpack n blocks.
+static int alltoall_derived(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                            MPI_Datatype recvtype, MPI_Comm comm) {
+    const long psize = dtype_size(recvtype) * recvcount;
+    if (sendbuf != MPI_IN_PLACE && dtype_size(sendtype) * sendcount != psize) return MPI_ERR_TRUNCATE;
+    if (psize == 0) return MPI_SUCCESS;
+    const int n = comm == MPI_COMM_SELF ? 1 : mv2h_size();
+    void *out = pool_get((size_t)psize * n), *in = out ? pool_get((size_t)psize * n) : nullptr;
+    if (!in) {
+        if (out) pool_put(out);
+        return MPI_ERR_NO_MEM;
+    }
+    int pos = 0, rc;
+    if (sendbuf == MPI_IN_PLACE) rc = PMPI_Pack(recvbuf, recvcount * n, recvtype, out, (int)(psize * n), &pos, comm);
+    else rc = PMPI_Pack(sendbuf, sendcount * n, sendtype, out, (int)(psize * n), &pos, comm);
+    if (!rc) rc = n > 1 ? mv2h_alltoall(out, in, (size_t)psize, nullptr) : mv2h_memcpy_dtod(in, out, (size_t)psize);
+    pos = 0;
+    if (!rc) rc = PMPI_Unpack(in, (int)(psize * n), &pos, recvbuf, recvcount * n, recvtype, comm);
+    pool_put(out);
+    pool_put(in);
+    return rc;
+}
+
+int PMPI_Alltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                  MPI_Datatype recvtype, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Alltoall";
+    if (const int rc = alltoall_checks(sendbuf, sendcount, sendtype, recvbuf, recvcount, recvtype, comm))
+        return err_return(comm_index(comm) < 0 ? MPI_COMM_WORLD : comm, rc, fn);
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    if (!dtype_is_contiguous(recvtype) || (!in_place && !dtype_is_contiguous(sendtype)))
+        return err_return(comm, alltoall_derived(sendbuf, sendcount, sendtype, recvbuf, recvcount, recvtype, comm), fn);
+    const size_t rbytes = (size_t)dtype_span(recvtype, recvcount);
+    if (!in_place && (size_t)dtype_span(sendtype, sendcount) != rbytes) return err_return(comm, MPI_ERR_TRUNCATE, fn);
+    if (rbytes == 0) return MPI_SUCCESS;
+    if (comm == MPI_COMM_SELF) {
+        int rc = MPI_SUCCESS;
+        if (!in_place) rc = is_dev(recvbuf) || is_dev(sendbuf) ? mv2h_memcpy_dtod(recvbuf, sendbuf, rbytes) : (memcpy(recvbuf, sendbuf, rbytes), 0);
+        return err_return(comm, rc, fn);
+    }
+    return err_return(comm, mv2h_alltoall(sendbuf, recvbuf, rbytes, nullptr), fn);
+}
+int MPI_Alltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                 MPI_Datatype recvtype, MPI_Comm comm) WEAK(MPI_Alltoall);
+
+// Contiguous types only: a non-contiguous type on either side is refused with
+// MPI_ERR_UNSUPPORTED_OPERATION (packing per pair is not built).  Counts and displacements are in
+// elements of their side's type, as in the reference; the runtime takes bytes.
+int PMPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype,
+                   void *recvbuf, const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Alltoallv";
+    if (!g_initialized || g_finalized) return err_return(comm, MPI_ERR_OTHER, fn);
+    if (comm_index(comm) < 0) return err_return(MPI_COMM_WORLD, MPI_ERR_COMM, fn);
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    if (!recvcounts || !rdispls || (!in_place && (!sendcounts || !sdispls))) return err_return(comm, MPI_ERR_ARG, fn);
+    const int n = comm == MPI_COMM_SELF ? 1 : mv2h_size();
+    long stotal = 0, rtotal = 0;
+    for (int j = 0; j < n; ++j) {
+        if (recvcounts[j] < 0 || (!in_place && sendcounts[j] < 0)) return err_return(comm, MPI_ERR_COUNT, fn);
+        rtotal += recvcounts[j];
+        if (!in_place) stotal += sendcounts[j];
+    }
+    if (!dtype_valid(recvtype) || (!in_place && !dtype_valid(sendtype))) return err_return(comm, MPI_ERR_TYPE, fn);
+    if (!dtype_committed(recvtype) || (!in_place && !dtype_committed(sendtype))) return err_return(comm, MPI_ERR_TYPE, fn);
+    if (!in_place && null_userbuf(sendbuf, stotal, sendtype)) return err_return(comm, MPI_ERR_BUFFER, fn);
+    if (inplace_buf(recvbuf, rtotal) || null_userbuf(recvbuf, rtotal, recvtype)) return err_return(comm, MPI_ERR_BUFFER, fn);
+    if (!in_place && stotal && rtotal && sendbuf == recvbuf) return err_return(comm, MPI_ERR_BUFFER, fn);
+    if (!dtype_is_contiguous(recvtype) || (!in_place && !dtype_is_contiguous(sendtype))) {
+        MV2_ERR("%s: non-contiguous datatypes are not supported", fn);
+        return err_return(comm, MPI_ERR_UNSUPPORTED_OPERATION, fn);
+    }
+    const size_t rext = (size_t)dtype_span(recvtype, 1), sext = in_place ? rext : (size_t)dtype_span(sendtype, 1);
+    std::vector<size_t> sb(n), so(n), rb(n), ro(n);
+    for (int j = 0; j < n; ++j) {
+        // a displacement matters only where its count is not zero
+        if ((recvcounts[j] && rdispls[j] < 0) || (!in_place && sendcounts[j] && sdispls[j] < 0))
+            return err_return(comm, MPI_ERR_ARG, fn);
+        rb[j] = (size_t)recvcounts[j] * rext;
+        ro[j] = recvcounts[j] ? (size_t)rdispls[j] * rext : 0;
+        sb[j] = in_place ? rb[j] : (size_t)sendcounts[j] * sext;
+        so[j] = in_place ? ro[j] : (sendcounts[j] ? (size_t)sdispls[j] * sext : 0);
+    }
+    if (comm == MPI_COMM_SELF) {
+        if (sb[0] != rb[0]) return err_return(comm, MPI_ERR_TRUNCATE, fn);
+        int rc = MPI_SUCCESS;
+        if (!in_place && rb[0]) {
+            void *d = (char *)recvbuf + ro[0];
+            const void *s = (const char *)sendbuf + so[0];
+            rc = is_dev(d) || is_dev(s) ? mv2h_memcpy_dtod(d, s, rb[0]) : (memcpy(d, s, rb[0]), 0);
+        }
+        return err_return(comm, rc, fn);
+    }
+    return err_return(comm, mv2h_alltoallv(sendbuf, sb.data(), so.data(), recvbuf, rb.data(), ro.data(), nullptr), fn);
+}
+int MPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype, void *recvbuf,
+                  const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm) WEAK(MPI_Alltoallv);
+
 int PMPI_Bcast(void *buffer, int count, MPI_Datatype dt, int root, MPI_Comm comm) {
     std::lock_guard<std::recursive_mutex> lk(g_cs);
     const char *fn = "MPI_Bcast";
@@ -926,6 +1045,29 @@ int PMPIX_Allgather_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sen
 }
 int MPIX_Allgather_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
                            MPI_Datatype recvtype, MPI_Comm comm, void *stream) WEAK(MPIX_Allgather_enqueue);
+
+int PMPIX_Alltoall_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                           MPI_Datatype recvtype, MPI_Comm comm, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPIX_Alltoall_enqueue";
+    if (const int rc = alltoall_checks(sendbuf, sendcount, sendtype, recvbuf, recvcount, recvtype, comm))
+        return err_return(comm_index(comm) < 0 ? MPI_COMM_WORLD : comm, rc, fn);
+    if (!stream) return err_return(comm, MPI_ERR_ARG, fn);
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    if (!dtype_is_contiguous(recvtype) || (!in_place && !dtype_is_contiguous(sendtype)))
+        return err_return(comm, MPI_ERR_TYPE, fn);
+    const size_t rbytes = (size_t)dtype_span(recvtype, recvcount);
+    if (!in_place && (size_t)dtype_span(sendtype, sendcount) != rbytes) return err_return(comm, MPI_ERR_TRUNCATE, fn);
+    if (rbytes == 0) return MPI_SUCCESS;
+    if (comm == MPI_COMM_SELF) {
+        if (in_place) return MPI_SUCCESS;
+        if (!is_dev(sendbuf) || !is_dev(recvbuf)) return err_return(comm, MPI_ERR_ARG, fn);
+        return err_return(comm, mv2h_copy_enqueue(recvbuf, sendbuf, rbytes, stream), fn);
+    }
+    return err_return(comm, mv2h_alltoall_enqueue(sendbuf, recvbuf, rbytes, stream), fn);
+}
+int MPIX_Alltoall_enqueue(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                          MPI_Datatype recvtype, MPI_Comm comm, void *stream) WEAK(MPIX_Alltoall_enqueue);
 
 int PMPIX_Bcast_enqueue(void *buffer, int count, MPI_Datatype dt, int root, MPI_Comm comm, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(g_cs);
@@ -1222,6 +1364,31 @@ int PMPI_Iallgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, v
 }
 int MPI_Iallgather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
                    MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request) WEAK(MPI_Iallgather);
+
+int PMPI_Ialltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                   MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Ialltoall", [&] {
+        return PMPI_Alltoall(sendbuf, sendcount, sendtype, recvbuf, recvcount, recvtype, comm);
+    });
+}
+int MPI_Ialltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                  MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request) WEAK(MPI_Ialltoall);
+
+// The ranks exchange their counts on the host at initiation (two host barriers), so initiation is
+// not local: it returns once every rank of the node has initiated the call.  The data moves behind
+// the request.
+int PMPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype,
+                    void *recvbuf, const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm,
+                    MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Ialltoallv", [&] {
+        return PMPI_Alltoallv(sendbuf, sendcounts, sdispls, sendtype, recvbuf, recvcounts, rdispls, recvtype, comm);
+    });
+}
+int MPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype, void *recvbuf,
+                   const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm,
+                   MPI_Request *request) WEAK(MPI_Ialltoallv);
 
 int PMPI_Ibcast(void *buffer, int count, MPI_Datatype dt, int root, MPI_Comm comm, MPI_Request *request) {
     std::lock_guard<std::recursive_mutex> lk(g_cs);

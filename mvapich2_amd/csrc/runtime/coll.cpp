@@ -85,6 +85,10 @@ static int scan_one_node_only(const char *name) {
     return E_OTHER;
 }
 
+// Several nodes: the follow-up is a pairwise exchange over the rank mesh; until then
+// both all-to-alls are refused like the scans, from the job's shape alone.
+static int alltoall_one_node_only(const char *name) { return scan_one_node_only(name); }
+
 static bool capturing(void *stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
@@ -204,6 +208,10 @@ int mv2h_get_info(const char *key, long *value) {
     else if (!strcmp(key, "code_load_us")) *value = (long)(w.code_load_ms * 1e3 + 0.5);
     else if (!strcmp(key, "selftest_calls")) *value = w.selftest_calls;
     else if (!strcmp(key, "selftest_scan_calls")) *value = w.selftest_scan_calls;
+    else if (!strcmp(key, "a2a_oneshot_vec")) *value = (long)a2a_path_calls(0);
+    else if (!strcmp(key, "a2a_oneshot_bytes")) *value = (long)a2a_path_calls(1);
+    else if (!strcmp(key, "a2a_pipe")) *value = (long)a2a_path_calls(2);
+    else if (!strcmp(key, "a2a_pipe_shift")) *value = (long)a2a_path_calls(3);
     else if (!strcmp(key, "call_allocs")) *value = (long)w.call_allocs;
     else if (!strcmp(key, "pool_trims")) *value = (long)w.pool_trims;
     else if (!strcmp(key, "rl_tiny_max")) *value = (long)w.rl_tiny_max;
@@ -553,6 +561,29 @@ int mv2h_allgather(const void *sendbuf, void *recvbuf, size_t bytes, void *strea
         [&] { return allgather_node(sendbuf, recvbuf, bytes, stream); });
 }
 
+int mv2h_alltoall(const void *sendbuf, void *recvbuf, size_t bytes, void *stream) {
+    if (int rc = alltoall_one_node_only("MPI_Alltoall")) return rc;
+    return alltoall_node(sendbuf, recvbuf, bytes, stream);
+}
+
+int mv2h_alltoallv(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, const size_t *rbytes,
+                   const size_t *roffs, void *stream) {
+    if (int rc = alltoall_one_node_only("MPI_Alltoallv")) return rc;
+    return alltoallv_node(sendbuf, sbytes, soffs, recvbuf, rbytes, roffs, stream);
+}
+
+int mv2h_alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned char *aligned16, int *path,
+                        int *grid, int *nrounds, size_t *maxlen) {
+    if (n < 1 || n > kMaxRanks || !slen || !rlen || !aligned16) return E_ARG;
+    A2APlan p{};
+    if (int rc = alltoallv_plan(n, slen, rlen, aligned16, &p)) return rc;
+    if (path) *path = p.path;
+    if (grid) *grid = p.grid;
+    if (nrounds) *nrounds = p.nrounds;
+    if (maxlen) *maxlen = p.maxlen;
+    return 0;
+}
+
 int mv2h_bcast(void *buffer, size_t bytes, int root, void *stream) {
     return node_or_mn(
         stream, [&] { return mn_bcast(buffer, bytes, root, stream); },
@@ -661,6 +692,15 @@ int mv2h_allgather_enqueue(const void *sendbuf, void *recvbuf, size_t bytes, voi
     if (rc || !bytes) return rc;
     EnqueueScope q(capturing(stream));
     return mv2h_allgather(sendbuf, recvbuf, bytes, stream);
+}
+
+// Capture into a HIP graph is refused (enqueue_checks without graph_ok): the kernels carry the
+// graph lane's reads of DevSeq, but no captured all-to-all has been replayed and checked yet.
+int mv2h_alltoall_enqueue(const void *sendbuf, void *recvbuf, size_t bytes, void *stream) {
+    int rc = bytes ? enqueue_checks(sendbuf, recvbuf, stream) : 0;
+    if (rc || !bytes) return rc;
+    EnqueueScope q;
+    return mv2h_alltoall(sendbuf, recvbuf, bytes, stream);
 }
 
 int mv2h_bcast_enqueue(void *buffer, size_t bytes, int root, void *stream) {

@@ -40,6 +40,23 @@ int reduce_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, in
 int reduce_scatter_entry(const void *sendbuf, void *recvbuf, const size_t *recvcounts, int dtype, int op, void *stream);
 int allgather_node(const void *sendbuf, void *recvbuf, size_t bytes, void *stream);
 int bcast_node(void *buffer, size_t bytes, int root, void *stream);
+// MPI_Alltoall / MPI_Alltoallv over this node's ranks (kernels: coll/alltoall.hip)
+int alltoall_node(const void *sendbuf, void *recvbuf, size_t bytes, void *stream);
+int alltoallv_node(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, const size_t *rbytes,
+                   const size_t *roffs, void *stream);
+// The plan of one Alltoallv from the whole matrix (slen[i * n + j]: bytes rank i sends rank j;
+// rlen[i * n + j]: bytes rank i expects from rank j; al16[i]: every offset of rank i is a multiple
+// of 16): a pure function of what every rank sees after the exchange and of the node's shared
+// limits.  E_TRUNCATE when a pair's two lengths differ.
+enum A2APath { A2A_NONE = 0, A2A_ONESHOT_VEC = 1, A2A_ONESHOT_BYTES = 2, A2A_PIPE = 3 };
+struct A2APlan {
+    int path, grid, nrounds;
+    size_t maxlen;
+};
+int alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned char *al16, A2APlan *out);
+// all-to-all calls by path (mv2h_get_info a2a_*): 0 one-shot vector, 1 one-shot byte-wise, 2 pipelined,
+// 3 those of the pipelined ones whose gather shifted at least one block
+uint64_t a2a_path_calls(int which);
 
 // ---- coll_mn.cpp: the collectives of a job on several nodes ----
 int mn_allreduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);

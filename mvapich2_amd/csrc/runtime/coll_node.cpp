@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "../../../include/mv2h.h"
+#include "../coll/alltoall.h"
 #include "coll_internal.h"
 #include "log.h"
 #include "pvars.h"
@@ -896,6 +897,279 @@ int node_allreduce_intra(const void *sendbuf, void *recvbuf, size_t count, int d
     if (rc) return rc;
     log_plan("allreduce (node step)", p, count);
     return allreduce_impl(sendbuf, recvbuf, count, dt, oi, pick_stream(stream), tree_from_plan(p, n, count, me));
+}
+
+// ---------------------------------------------------------------------------
+// MPI_Alltoall / MPI_Alltoallv (kernels: coll/alltoall.hip).
+//
+// Both calls end in the same launch: a table of what this rank sends to and receives from every
+// rank (offset, length, and the misalignment each incoming block carries), moved by the one-shot
+// kernel when every pair is small and by the pipelined kernel otherwise.  The path, the grid and
+// the round count read only values every rank shares: for MPI_Alltoall the block size, for
+// MPI_Alltoallv the whole matrix of pair lengths, which the ranks publish in the control segment
+// and read behind a host barrier (send counts are local knowledge; the longest pair of the job
+// decides the geometry).
+// ---------------------------------------------------------------------------
+static uint64_t g_a2a_paths[4];  // calls by path (a2a_path_calls)
+static uint64_t g_a2a_seq;       // MPI_Alltoallv calls issued (the published rows' sequence number)
+uint64_t a2a_path_calls(int which) { return which >= 0 && which < 4 ? g_a2a_paths[which] : 0; }
+
+// blocks of any size up to this move byte by byte through the one-shot kernel (allgather_node's limit)
+constexpr size_t kA2ABytewise = 2048;
+
+// Path and geometry from the longest pair, whether every pair is a whole number of 16-byte
+// vectors on 16-byte offsets, and the node's shared limits.
+static A2APlan plan_from(size_t maxlen, bool vec) {
+    World &w = world();
+    A2APlan p{};
+    p.maxlen = maxlen;
+    if (!maxlen) return p;
+    if ((vec || maxlen <= kA2ABytewise) && maxlen <= std::min(w.oneshot_max, w.slot_bytes)) {
+        p.path = vec ? A2A_ONESHOT_VEC : A2A_ONESHOT_BYTES;
+        p.grid = oneshot_grid(vec ? maxlen / 16 : 0, grid_cap());
+        p.nrounds = 1;
+    } else {
+        const PipeGeom g = pipe_geom(maxlen);
+        p.path = A2A_PIPE;
+        p.grid = g.grid;
+        p.nrounds = g.nrounds;
+    }
+    return p;
+}
+
+int alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned char *al16, A2APlan *out) {
+    size_t maxlen = 0;
+    bool vec = true, trunc = false;
+    for (int i = 0; i < n; ++i) {
+        vec = vec && al16[i];
+        for (int j = 0; j < n; ++j) {
+            trunc = trunc || slen[i * n + j] != rlen[j * n + i];
+            maxlen = std::max(maxlen, slen[i * n + j]);
+            vec = vec && slen[i * n + j] % 16 == 0;
+        }
+    }
+    if (trunc) return E_TRUNCATE;
+    *out = plan_from(maxlen, vec);
+    return 0;
+}
+
+// Launch the planned kernel on the table in `a` (send / recv 16-byte aligned device memory, or any
+// device memory on the byte-wise path).  Epochs, rounds and one-shot calls are reserved as every
+// other collective reserves them, so every rank advances w.epoch, w.round and w.os_calls alike.
+static int a2a_launch(A2AArgs &a, const A2APlan &p, hipStream_t st) {
+    World &w = world();
+    a.n = w.size;
+    a.me = w.rank;
+    bool shifted = false;
+    for (int j = 0; j < a.n; ++j)
+        shifted = shifted || (j != a.me && a.rlen[j] && a.smis[j] != (uint32_t)(a.roff[j] & 15));
+    int rc;
+    if (p.path == A2A_PIPE) {
+        // rounds and epochs exactly as run_pipe reserves them (it launches what it reserves, so the
+        // lines are restated here): nrounds rounds of slot parities, 2 * nrounds flag epochs
+        const PipeGeom g = pipe_geom(p.maxlen);
+        a.tseg = g.tseg;
+        a.tsub = g.tsub;
+        a.nrounds = g.nrounds;
+        a.rnt = w.pipe_rnt;
+        if (w.graph) {  // graph lane: own arenas and flags; epochs and parities from the device
+            a.ag_peer = w.g_peer_ag;
+            a.sig_peer = w.g_peer_sig;
+            a.sig_own = w.g_sig;
+            a.dseq = w.dseq;
+        } else {
+            a.ag_peer = w.peer_ag;
+            a.sig_peer = w.peer_sig;
+            a.sig_own = w.sig;
+            a.round0 = w.round;
+            w.round += (uint64_t)g.nrounds;
+            a.epoch0 = w.epoch + 1;
+            w.epoch += 2 * (uint64_t)g.nrounds;
+            log_epochs(a.epoch0, w.epoch, st);
+        }
+        a.err = w.h_err;
+        a.timeout = w.timeout_ticks;
+        a.light = w.light_release;
+        a.done = arm_done(st);
+        ++g_a2a_paths[2];
+        if (shifted) ++g_a2a_paths[3];
+        MV2_DEBUG("alltoall pipelined grid %d tsub %zu rounds %d maxlen %zu%s", g.grid, g.tsub, g.nrounds, p.maxlen,
+                  shifted ? " (shifted gather)" : "");
+        tmark0(st);
+        rc = launch_pipe_a2a(a, coll_cfg(g.grid, st));
+        tmark1(st);
+    } else {
+        OneShotArgs o{};
+        oneshot_common(o, st);
+        a.arena_peer = o.arena_peer;
+        a.arena_own = o.arena_own;
+        a.slot_bytes = o.slot_bytes;
+        a.half = o.half;
+        a.sig_peer = o.sig_peer;
+        a.sig_own = o.sig_own;
+        a.epoch0 = o.epoch;
+        a.light = o.light;
+        a.err = o.err;
+        a.timeout = o.timeout;
+        a.done = o.done;
+        a.dseq = o.dseq;
+        a.nvec = p.path == A2A_ONESHOT_VEC ? p.maxlen / 16 : 0;
+        ++g_a2a_paths[p.path == A2A_ONESHOT_VEC ? 0 : 1];
+        tmark0(st);
+        rc = launch_oneshot_a2a(a, coll_cfg(p.grid, st));
+        tmark1(st);
+    }
+    return rc;
+}
+
+int alltoall_node(const void *sendbuf, void *recvbuf, size_t bytes, void *stream) {
+    hp_entry();
+    int rc;
+    if ((rc = require_world())) return rc;
+    if (bytes == 0) return 0;
+    World &w = world();
+    hipStream_t st = pick_stream(stream);
+    const int n = w.size, me = w.rank;
+    const bool in_place = sendbuf == (const void *)-1;
+    if (n == 1) {
+        if (!in_place && hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDefault, st) != hipSuccess) return E_INTERN;
+        return finish(st, false);
+    }
+    const size_t total = bytes * (size_t)n;
+    const A2APlan p = plan_from(bytes, bytes % 16 == 0);
+    // Blocks lie back to back, so block j starts at j * bytes whatever that is modulo 16: only a
+    // base that is not 16-byte aligned (or host memory) is staged.  The byte-wise path reads its
+    // send buffer byte by byte and takes any device address.
+    const bool direct = is_device(recvbuf) && (uintptr_t)recvbuf % 16 == 0;
+    char *dst = direct ? (char *)recvbuf : (char *)call_scratch(1, total);
+    if (!dst) return E_NO_MEM;
+    if (in_place && !direct) hipMemcpyAsync(dst, recvbuf, total, hipMemcpyDefault, st);
+    const char *src = dst;
+    if (!in_place) {
+        src = (const char *)sendbuf;
+        if (!(is_device(sendbuf) && (p.path == A2A_ONESHOT_BYTES || (uintptr_t)sendbuf % 16 == 0))) {
+            char *t = (char *)call_scratch(0, total);
+            if (!t) return E_NO_MEM;
+            beacon(BC_STAGE);
+            hipMemcpyAsync(t, sendbuf, total, hipMemcpyDefault, st);
+            src = t;
+        }
+    }
+    A2AArgs a{};
+    a.send = src;
+    a.recv = dst;
+    for (int j = 0; j < n; ++j) {
+        a.soff[j] = a.roff[j] = (size_t)j * bytes;
+        a.slen[j] = a.rlen[j] = bytes;
+        a.smis[j] = (uint32_t)(((size_t)me * bytes) & 15);  // rank j's block for me starts at me * bytes there
+    }
+    if ((rc = a2a_launch(a, p, st))) return rc;
+    if (!direct && enq_copy_last(recvbuf, dst, total, st) != hipSuccess) return E_INTERN;
+    return finish(st, w.timing);
+}
+
+int alltoallv_node(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, const size_t *rbytes,
+                   const size_t *roffs, void *stream) {
+    hp_entry();
+    int rc;
+    if ((rc = require_world())) return rc;
+    if (!rbytes || !roffs) return E_ARG;
+    World &w = world();
+    const int n = w.size, me = w.rank;
+    const bool in_place = sendbuf == (const void *)-1;
+    if (in_place) {
+        sbytes = rbytes;
+        soffs = roffs;
+    } else if (!sbytes || !soffs) {
+        return E_ARG;
+    }
+    hipStream_t st = pick_stream(stream);
+    if (n == 1) {
+        if (sbytes[0] != rbytes[0]) return E_TRUNCATE;
+        if (!in_place && sbytes[0] &&
+            hipMemcpyAsync((char *)recvbuf + roffs[0], (const char *)sendbuf + soffs[0], sbytes[0], hipMemcpyDefault, st) !=
+                hipSuccess)
+            return E_INTERN;
+        return finish(st, false);
+    }
+    // publish my row, meet, read the matrix, meet again (nobody rewrites its row for the next call
+    // before every rank has read this one)
+    A2ARow &mine = w.shm->a2a[me];
+    mine.seq = ++g_a2a_seq;
+    bool al16 = true;
+    size_t sspan = 0, rspan = 0;
+    for (int j = 0; j < n; ++j) {
+        mine.slen[j] = sbytes[j];
+        mine.rlen[j] = rbytes[j];
+        mine.smis[j] = (uint8_t)(soffs[j] & 15);
+        al16 = al16 && soffs[j] % 16 == 0 && roffs[j] % 16 == 0;
+        if (sbytes[j]) sspan = std::max(sspan, soffs[j] + sbytes[j]);
+        if (rbytes[j]) rspan = std::max(rspan, roffs[j] + rbytes[j]);
+    }
+    mine.al16 = al16;
+    host_barrier();
+    size_t slen[kMaxRanks * kMaxRanks], rlen[kMaxRanks * kMaxRanks];
+    unsigned char al[kMaxRanks];
+    uint32_t smis[kMaxRanks];
+    bool same_call = true;
+    for (int i = 0; i < n; ++i) {
+        const A2ARow &r = w.shm->a2a[i];
+        same_call = same_call && r.seq == mine.seq;
+        al[i] = r.al16;
+        smis[i] = r.smis[me];
+        for (int j = 0; j < n; ++j) {
+            slen[i * n + j] = (size_t)r.slen[j];
+            rlen[i * n + j] = (size_t)r.rlen[j];
+        }
+    }
+    host_barrier();
+    if (!same_call) {
+        MV2_ERR("MPI_Alltoallv: the ranks of the node are not in the same call");
+        return E_OTHER;
+    }
+    A2APlan p{};
+    if ((rc = alltoallv_plan(n, slen, rlen, al, &p))) {
+        MV2_ERR("MPI_Alltoallv: a pair's send and receive lengths differ");
+        return rc;
+    }
+    if (p.path == A2A_NONE) return 0;  // every pair is empty, on every rank
+    // Staging.  Only bytes of receive blocks may be written, so a staged receive buffer is copied
+    // back block by block; the send side is staged block by block too (a gap need not be readable).
+    const bool bytewise = p.path == A2A_ONESHOT_BYTES;
+    const bool direct = is_device(recvbuf) && (bytewise || (uintptr_t)recvbuf % 16 == 0);
+    char *dst = direct ? (char *)recvbuf : (char *)call_scratch(1, std::max<size_t>(rspan, 16));
+    if (!dst) return E_NO_MEM;
+    const char *src = dst;
+    if (in_place) {
+        if (!direct)
+            for (int j = 0; j < n; ++j)
+                if (rbytes[j]) hipMemcpyAsync(dst + roffs[j], (char *)recvbuf + roffs[j], rbytes[j], hipMemcpyDefault, st);
+    } else if (is_device(sendbuf) && (bytewise || (uintptr_t)sendbuf % 16 == 0)) {
+        src = (const char *)sendbuf;
+    } else {
+        char *t = (char *)call_scratch(0, std::max<size_t>(sspan, 16));
+        if (!t) return E_NO_MEM;
+        beacon(BC_STAGE);
+        for (int j = 0; j < n; ++j)
+            if (sbytes[j]) hipMemcpyAsync(t + soffs[j], (const char *)sendbuf + soffs[j], sbytes[j], hipMemcpyDefault, st);
+        src = t;
+    }
+    A2AArgs a{};
+    a.send = src;
+    a.recv = dst;
+    for (int j = 0; j < n; ++j) {
+        a.soff[j] = soffs[j];
+        a.slen[j] = sbytes[j];
+        a.roff[j] = roffs[j];
+        a.rlen[j] = rbytes[j];
+        a.smis[j] = smis[j];
+    }
+    if ((rc = a2a_launch(a, p, st))) return rc;
+    if (!direct)
+        for (int j = 0; j < n; ++j)
+            if (rbytes[j] && enq_copy((char *)recvbuf + roffs[j], dst + roffs[j], rbytes[j], st) != hipSuccess)
+                return E_INTERN;
+    return finish(st, w.timing);
 }
 
 }  // namespace mv2

@@ -86,6 +86,16 @@ struct alignas(64) ShmRank {
     std::atomic<uint32_t> bh_pos;
 };
 
+// One rank's row of an MPI_Alltoallv (coll_node.cpp): what it sends to and expects from every rank
+// of the node, published for the call numbered `seq` so that every rank plans from the whole matrix
+struct A2ARow {
+    uint64_t seq;
+    uint64_t slen[kMaxRanks];  // bytes this rank sends rank j
+    uint64_t rlen[kMaxRanks];  // bytes this rank expects from rank j
+    uint8_t smis[kMaxRanks];   // (offset of the block for rank j in the send buffer) & 15
+    uint8_t al16;              // every send and receive offset of this rank is a multiple of 16
+};
+
 constexpr int kHwsProcs = 8;  // processes one GPU's hardware scheduler runs at once (KFD's VMIDs)
 constexpr int kMeshMaxRanks = 64;  // jobs up to this many ranks get the rank mesh (p2p across nodes)
 
@@ -99,6 +109,7 @@ struct ShmSeg {
     P2PChan chan[kMaxRanks][kMaxRanks];  // [src][dst]
     int mesh_port[kMeshMaxRanks];        // every rank's rank-mesh listener (the leader fills it in)
     char node_ip[kMeshMaxRanks][48];     // every node's address
+    A2ARow a2a[kMaxRanks];               // MPI_Alltoallv: every rank's row of the current call
 };
 
 struct World {
