@@ -98,6 +98,30 @@ int mv2h_alltoallv(const void *sendbuf, const size_t *sbytes, const size_t *soff
  * MPI_ERR_TRUNCATE's class when a pair's two lengths differ. */
 int mv2h_alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned char *aligned16, int *path,
                         int *grid, int *nrounds, size_t *maxlen);
+/* MPI_Allgatherv, MPI_Gather(v), MPI_Scatter(v) on one node (MPIR_Allgatherv_MV2 allgatherv_osu.c:1146,
+ * MPIR_Gather_MV2 gather_osu.c:2122, MPIR_Gatherv_MV2 gatherv_osu.c:41, MPIR_Scatter_MV2
+ * scatter_osu.c:2181, MPIR_Scatterv scatterv.c:168), byte counts and byte offsets.  (void *)-1 is
+ * MPI_IN_PLACE: as sendbuf of Allgatherv (the own block is read from recvbuf + roffs[me]) and of
+ * Gather(v) at the root (its block is already in place), as recvbuf of Scatter(v) at the root (its
+ * block is not moved).  rbytes / roffs of Gather(v) and sbytes / soffs of Scatter(v) are read at the
+ * root only; a non-root's recvbuf (Gather) or sendbuf (Scatter) is never dereferenced and may be
+ * null.  Only bytes of receive blocks are written.  Allgatherv takes the whole rbytes vector on
+ * every rank and checks sbytes == rbytes[me] locally (MPI_ERR_TRUNCATE's class); vectors that
+ * differ between the ranks are erroneous and end in the kernels' timeout (MPI_ERR_OTHER's class).
+ * Gatherv / Scatterv meet on the host inside the call: a pair whose two lengths differ returns
+ * MPI_ERR_TRUNCATE's class on every rank before any device work.  A job over several nodes is
+ * refused with MPI_ERR_OTHER's class before any device work. */
+int mv2h_allgatherv(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes,
+                    const size_t *roffs, void *stream);
+int mv2h_gather(const void *sendbuf, void *recvbuf, size_t bytes_per_rank, int root, void *stream);
+int mv2h_gatherv(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes,
+                 const size_t *roffs, int root, void *stream);
+int mv2h_scatter(const void *sendbuf, void *recvbuf, size_t bytes_per_rank, int root, void *stream);
+int mv2h_scatterv(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf,
+                  size_t rbytes, int root, void *stream);
+/* Test hook: the plan every rank derives for one Allgatherv / Gather from the n block lengths and
+ * the node's shared limits (paths as mv2h_alltoallv_plan's).  It reads no displacement or address. */
+int mv2h_gv_plan(int n, const size_t *len, int *path, int *grid, int *nrounds, size_t *maxlen);
 int mv2h_barrier(void);
 
 /* ---- stream-ordered collectives (SURVEY §8(f) rank 3 "stream-ordered variants") ----
@@ -302,6 +326,8 @@ int mv2h_set_tuning(const char *key, long value);
  * wall time and its parts), "selftest_calls" (collective calls MPI_Init's self-test checked),
  * "a2a_oneshot_vec" / "a2a_oneshot_bytes" / "a2a_pipe" / "a2a_pipe_shift" (all-to-all calls by path: one-shot by vectors, one-shot byte by
  * byte, pipelined, and those of the pipelined ones whose gather shifted a block),
+ * "gv_oneshot_vec" / "gv_oneshot_bytes" / "gv_pipe" / "gv_pipe_shift" (the same for the gather-table
+ * kernels of MPI_Allgatherv and MPI_Gather; Gatherv and Scatter(v) count under a2a_*),
  * "call_allocs" (device allocations made inside MPI calls: scratch growth, pooled temporaries),
  * "hw_queues_set" (GPU_MAX_HW_QUEUES set before HIP started; negative: wanted, but HIP was already
  * running), "rl_tiny_max" / "rl_grid" / "max_grid" (the launch tunings of the same names as they stand:

@@ -63,6 +63,13 @@ def lib():
                             ctypes.POINTER(c_sz), c_vp], c_int),
         "mv2h_alltoallv_plan": ([c_int, ctypes.POINTER(c_sz), ctypes.POINTER(c_sz), ctypes.c_char_p, ctypes.POINTER(c_int),
                                  ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_sz)], c_int),
+        "mv2h_allgatherv": ([c_vp, c_sz, c_vp, ctypes.POINTER(c_sz), ctypes.POINTER(c_sz), c_vp], c_int),
+        "mv2h_gather": ([c_vp, c_vp, c_sz, c_int, c_vp], c_int),
+        "mv2h_gatherv": ([c_vp, c_sz, c_vp, ctypes.POINTER(c_sz), ctypes.POINTER(c_sz), c_int, c_vp], c_int),
+        "mv2h_scatter": ([c_vp, c_vp, c_sz, c_int, c_vp], c_int),
+        "mv2h_scatterv": ([c_vp, ctypes.POINTER(c_sz), ctypes.POINTER(c_sz), c_vp, c_sz, c_int, c_vp], c_int),
+        "mv2h_gv_plan": ([c_int, ctypes.POINTER(c_sz), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                          ctypes.POINTER(c_sz)], c_int),
         "mv2h_barrier": ([], c_int),
         "mv2h_pack_strided": ([c_vp, c_vp, c_sz, c_sz, c_sz, c_vp], c_int),
         "mv2h_unpack_strided": ([c_vp, c_vp, c_sz, c_sz, c_sz, c_vp], c_int),
@@ -110,6 +117,11 @@ def lib():
         "MPI_Alltoall": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int], c_int),
         "MPI_Alltoallv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, ctypes.POINTER(c_int),
                            ctypes.POINTER(c_int), c_int, c_int], c_int),
+        "MPI_Gather": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int], c_int),
+        "MPI_Gatherv": ([c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_int], c_int),
+        "MPI_Scatter": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int], c_int),
+        "MPI_Scatterv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, c_int, c_int, c_int, c_int], c_int),
+        "MPI_Allgatherv": ([c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int], c_int),
         "MPI_Op_create": ([c_vp, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Op_free": ([ctypes.POINTER(c_int)], c_int),
         "MPI_Type_vector": ([c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
@@ -144,6 +156,14 @@ def lib():
         "MPI_Ialltoall": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Ialltoallv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, ctypes.POINTER(c_int),
                             ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int)], c_int),
+        "MPI_Igather": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
+        "MPI_Igatherv": ([c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_int,
+                          ctypes.POINTER(c_int)], c_int),
+        "MPI_Iscatter": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
+        "MPI_Iscatterv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, c_int, c_int, c_int, c_int,
+                           ctypes.POINTER(c_int)], c_int),
+        "MPI_Iallgatherv": ([c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int,
+                             ctypes.POINTER(c_int)], c_int),
         "MPI_Ibarrier": ([c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Wait": ([ctypes.POINTER(c_int), c_vp], c_int),
         "MPI_Test": ([ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp], c_int),
@@ -263,7 +283,53 @@ def alltoallv_plan(slen, rlen=None, aligned16=None):
     return rc, A2A_PATHS[path.value], grid.value, rounds.value, maxlen.value
 
 
+def _sz(v):
+    return (ctypes.c_size_t * len(v))(*v) if v is not None else None
+
+
+def _ptr(buf):
+    """a DeviceBuffer's address; None: MPI_IN_PLACE; 0: a null pointer (a side that is not significant)"""
+    if buf is None:
+        return ctypes.c_void_p(-1)
+    return ctypes.c_void_p(buf if isinstance(buf, int) else buf.ptr)
+
+
+def allgatherv(sendbuf, sbytes, recvbuf, rbytes, roffs):
+    """MPI_Allgatherv in bytes on device buffers (mv2h_allgatherv); sendbuf=None: MPI_IN_PLACE."""
+    return lib().mv2h_allgatherv(_ptr(sendbuf), sbytes, _ptr(recvbuf), _sz(rbytes), _sz(roffs), None)
+
+
+def gather(sendbuf, recvbuf, bytes_per_rank, root):
+    """MPI_Gather in bytes (mv2h_gather); sendbuf=None at the root: MPI_IN_PLACE; recvbuf=0 elsewhere."""
+    return lib().mv2h_gather(_ptr(sendbuf), _ptr(recvbuf), bytes_per_rank, root, None)
+
+
+def gatherv(sendbuf, sbytes, recvbuf, rbytes, roffs, root):
+    """MPI_Gatherv in bytes (mv2h_gatherv); rbytes / roffs matter at the root only."""
+    return lib().mv2h_gatherv(_ptr(sendbuf), sbytes, _ptr(recvbuf), _sz(rbytes), _sz(roffs), root, None)
+
+
+def scatter(sendbuf, recvbuf, bytes_per_rank, root):
+    """MPI_Scatter in bytes (mv2h_scatter); recvbuf=None at the root: MPI_IN_PLACE; sendbuf=0 elsewhere."""
+    return lib().mv2h_scatter(_ptr(sendbuf), _ptr(recvbuf), bytes_per_rank, root, None)
+
+
+def scatterv(sendbuf, sbytes, soffs, recvbuf, rbytes, root):
+    """MPI_Scatterv in bytes (mv2h_scatterv); sbytes / soffs matter at the root only."""
+    return lib().mv2h_scatterv(_ptr(sendbuf), _sz(sbytes), _sz(soffs), _ptr(recvbuf), rbytes, root, None)
+
+
+def gv_plan(lens):
+    """(rc, path, grid, nrounds, maxlen) every rank derives for one MPI_Allgatherv / MPI_Gather from
+    the n block lengths (mv2h_gv_plan); paths as alltoallv_plan's."""
+    path, grid, rounds, maxlen = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    rc = lib().mv2h_gv_plan(len(lens), _sz(lens), ctypes.byref(path), ctypes.byref(grid), ctypes.byref(rounds),
+                            ctypes.byref(maxlen))
+    return rc, A2A_PATHS[path.value], grid.value, rounds.value, maxlen.value
+
+
 __all__ = ["lib", "check", "DeviceBuffer", "MPIError", "reduce_local", "alltoall", "alltoallv", "alltoallv_plan",
+           "allgatherv", "gather", "gatherv", "scatter", "scatterv", "gv_plan",
            "np_dtype", "consts", "OPS", "TYPES"]
 
 

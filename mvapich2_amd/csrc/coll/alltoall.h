@@ -37,7 +37,42 @@ struct A2AArgs {
     DevSeq *dseq;  // graph lane
 };
 
+// One gather over this node's ranks (MPI_Allgatherv: every rank receives; MPI_Gather: the root
+// alone).  Rank me has one block, slen bytes at send, for the ranks of dmask; the own bit means
+// "also copy it to my own recv + roff[me], unless it is already there".  It gathers rlen[j] bytes
+// from rank j at recv + roff[j] (rlen[j] on rank me equals rank j's slen where rank j's dmask
+// names me; all zero on a rank outside every mask; rlen[me] is not read).  send is 16-byte
+// aligned, or any device address on the byte-wise path; the one-shot vector path also wants
+// recv + roff[j] 16-byte aligned (the runtime stages anything else).
+struct GvArgs {
+    int n, me;
+    const char *send;
+    size_t slen;
+    unsigned dmask;
+    char *recv;
+    size_t roff[kMaxRanks], rlen[kMaxRanks];
+    // the rest as in A2AArgs
+    PeerTableW arena_peer;
+    const char *arena_own;
+    size_t nvec, slot_bytes, half;
+    PeerTableW ag_peer;
+    size_t tseg, tsub;
+    uint64_t round0;
+    int nrounds;
+    int rnt;
+    SigTable sig_peer;
+    uint64_t *sig_own;
+    uint64_t epoch0;
+    int light;
+    int *err;
+    uint64_t timeout;
+    Done done;
+    DevSeq *dseq;
+};
+
 int launch_oneshot_a2a(const A2AArgs &a, const LaunchCfg &cfg);
 int launch_pipe_a2a(const A2AArgs &a, const LaunchCfg &cfg);
+int launch_oneshot_gv(const GvArgs &a, const LaunchCfg &cfg);
+int launch_pipe_gv(const GvArgs &a, const LaunchCfg &cfg);
 
 }  // namespace mv2

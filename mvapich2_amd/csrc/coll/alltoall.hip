@@ -267,4 +267,148 @@ int launch_pipe_a2a(const A2AArgs &a, const LaunchCfg &cfg) {
     return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
 }
 
+// ---------------------------------------------------------------------------
+// MPI_Allgatherv / MPI_Gather: every rank has one block, and it goes to a set of ranks (dmask:
+// all of them, or the root alone).  Through the table above an allgatherv push would be n - 1
+// jobs that each read the same source range again; here a vector is loaded once and stored to
+// every masked destination (PIPE_AG's blk_copy_multi).  The source is 16-byte aligned (the runtime
+// stages anything else), so a block lies in slot [me] of every destination's arena at
+// misalignment 0, every store into a peer is a whole aligned vector and no misalignment has to be
+// exchanged; the receiver's gather shifts where its own destination is off a 16-byte boundary.
+//
+// Flags, epochs, arena halves and slot parities are the kernels' above, and the reuse argument
+// with them: every rank raises and awaits every flag in every round, whatever its mask and
+// lengths, because passing a wait has to prove that every peer has left the previous call --
+// which may have been any other collective.
+// ---------------------------------------------------------------------------
+
+// One-shot: nvec > 0: every length is a multiple of 16, send, recv and every roff are 16-byte
+// aligned, and workgroup b moves vectors [b * per, (b + 1) * per) of every block; nvec == 0:
+// workgroup 0 moves every block byte by byte (any address).
+__global__ __launch_bounds__(kThreads) void k_oneshot_gv(GvArgs a) {
+    const int blk = blockIdx.x, G = gridDim.x;
+    const size_t per = (a.nvec + G - 1) / G;
+    const size_t vb = (size_t)blk * per, ve = vb + per;
+    uint64_t epoch = a.epoch0;
+    size_t poff = 0;
+    if (a.dseq) {  // graph lane: this replay's epoch and arena half
+        const SeqBase q = dseq_read(a.dseq);
+        epoch = q.epoch + 1;
+        poff = (q.os & 1) * a.half;
+    }
+    const size_t myslot = poff + (size_t)a.me * a.slot_bytes;
+    // the own bit: also to my own recv + roff[me], unless the block is already there
+    char *own = a.recv + a.roff[a.me];
+    if (!((a.dmask >> a.me) & 1u) || own == a.send) own = nullptr;
+    const unsigned peers = a.dmask & ~(1u << a.me);
+    if (peers || own) {
+        if (a.nvec) {
+            const size_t nv = a.slen >> 4, e = ve < nv ? ve : nv;
+            for (size_t i = vb + threadIdx.x; i < e; i += kThreads) {
+                const v4u v = ((const v4u *)a.send)[i];
+#pragma unroll
+                for (int j = 0; j < kMaxRanks; ++j)
+                    if (j < a.n && ((peers >> j) & 1u)) ((v4u *)(a.arena_peer.p[j] + myslot))[i] = v;
+                if (own) ((v4u *)own)[i] = v;
+            }
+        } else if (blk == 0) {
+            for (size_t i = threadIdx.x; i < a.slen; i += kThreads) {
+                const char c = a.send[i];
+#pragma unroll
+                for (int j = 0; j < kMaxRanks; ++j)
+                    if (j < a.n && ((peers >> j) & 1u)) (a.arena_peer.p[j] + myslot)[i] = c;
+                if (own) own[i] = c;
+            }
+        }
+    }
+    signal_peers(a.sig_peer, a.n, a.me, blk, epoch, a.light != 0);
+    if (wait_peers(a.sig_own, a.n, blk, epoch, a.err, a.timeout, a.light != 0)) {
+#pragma unroll
+        for (int j = 0; j < kMaxRanks; ++j) {
+            if (j >= a.n || j == a.me) continue;
+            const char *slot = a.arena_own + poff + (size_t)j * a.slot_bytes;
+            char *dst = a.recv + a.roff[j];
+            const size_t len = a.rlen[j];
+            if (a.nvec) {
+                const size_t nv = len >> 4, e = ve < nv ? ve : nv;
+                for (size_t i = vb + threadIdx.x; i < e; i += kThreads) ((v4u *)dst)[i] = ld_nt((const v4u *)slot + i);
+            } else if (blk == 0) {
+                for (size_t i = threadIdx.x; i < len; i += kThreads) dst[i] = __builtin_nontemporal_load(slot + i);
+            }
+        }
+    }
+    if (a.dseq) dseq_advance(a.dseq, 1, 0, 1);
+    block_done(a.done);
+}
+
+// Pipelined: k_pipe_a2a's tiling, parities and flags.  Round k:
+//   push   : my round's range -> pslot(rank j's AG region, par, me) + b * tsub for every masked
+//            j != me and, with the own bit, to recv + roff[me], in one blk_copy_multi (the own
+//            destination apart, shifted, where it is off a 16-byte boundary)
+//   E(k)   : signal every peer, wait for every peer
+//   gather : slot [par][j] + b * tsub -> recv + roff[j] + range, shifted where that is off a
+//            16-byte boundary
+__global__ __launch_bounds__(kPipeThreads) void k_pipe_gv(GvArgs a) {
+    uint64_t epoch0 = a.epoch0, round0 = a.round0;
+    if (a.dseq) {  // graph lane: this replay's base, read before any workgroup can advance it
+        const SeqBase q = dseq_read(a.dseq);
+        epoch0 = q.epoch + 1;
+        round0 = q.round;
+    }
+    const int b = blockIdx.x, n = a.n, me = a.me;
+    const unsigned all = (1u << n) - 1u;
+    const unsigned peers = a.dmask & ~(1u << me);
+    const size_t so = (size_t)b * a.tsub;
+    char *own = a.recv + a.roff[me];
+    if (!((a.dmask >> me) & 1u) || own == a.send) own = nullptr;
+    for (int k = 0; k < a.nrounds; ++k) {
+        const uint64_t par = (round0 + (uint64_t)k) & 1;
+        const uint64_t E = epoch0 + 2 * (uint64_t)k;
+        const size_t rbase = (size_t)k * a.tseg + so;
+        const size_t len = a2a_range(a.slen, rbase, a.tsub);
+        if (len && (peers || own)) {
+            const bool own_eq = own && ((uintptr_t)own & 15) == 0;
+            Dsts d{};
+#pragma unroll
+            for (int j = 0; j < kMaxRanks; ++j)
+                if (j < n && ((peers >> j) & 1u)) d.p[j] = pslot(a.ag_peer.p[j], par, me) + so;
+            if (own_eq) d.p[kMaxRanks] = own + rbase;
+            if (peers || own_eq) blk_copy_multi(d, a.send + rbase, len, a.rnt != 0);
+            if (own && !own_eq) {
+                Jobs o{};
+                o.src[0] = a.send + rbase;
+                o.dst[0] = own + rbase;
+                o.len[0] = len;
+                blk_copy_shift(o);
+            }
+        }
+        signal_peers(a.sig_peer, n, me, b, E, a.light != 0);
+        if (!wait_mask(a.sig_own, all, b, E, a.err, a.timeout, a.light != 0)) break;
+        Jobs g{};
+#pragma unroll
+        for (int j = 0; j < kMaxRanks; ++j) {
+            if (j < n && j != me) {
+                g.src[j] = pslot(a.ag_peer.p[me], par, j) + so;
+                g.dst[j] = a.recv + a.roff[j] + rbase;
+                g.len[j] = a2a_range(a.rlen[j], rbase, a.tsub);
+            }
+        }
+        blk_copy_local(g);
+    }
+    if (a.dseq) dseq_advance(a.dseq, 2 * (uint64_t)a.nrounds, (uint64_t)a.nrounds, 0);
+    block_done(a.done);
+}
+
+int launch_oneshot_gv(const GvArgs &a, const LaunchCfg &cfg) {
+    static const int cap = resident_grid((const void *)k_oneshot_gv, cfg);
+    const int g = cfg.grid < cap ? cfg.grid : cap;
+    hipLaunchKernelGGL(k_oneshot_gv, dim3(g), dim3(kThreads), 0, cfg.stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+}
+
+int launch_pipe_gv(const GvArgs &a, const LaunchCfg &cfg) {
+    hipLaunchKernelGGL(k_pipe_gv, dim3(cfg.grid), dim3(kPipeThreads), 0, cfg.stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+}
+
 }  // namespace mv2

@@ -910,6 +910,357 @@ int PMPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispl
 int MPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype, void *recvbuf,
                   const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm) WEAK(MPI_Alltoallv);
 
+// ---------------------------------------------------------------------------
+// MPI_Gather(v) / MPI_Scatter(v) / MPI_Allgatherv.  Checks after gather.c:823-905, gatherv.c:
+// 300-400, scatter.c:740-820, scatterv.c:240-330 and allgatherv.c:1090-1160: communicator, root,
+// then per significant side count, type, committed and buffer; MPI_IN_PLACE only where the call
+// has it (the send buffer of Allgatherv and of the root's Gather(v), the receive buffer of the
+// root's Scatter(v)); the n-block side matters at the root only; a displacement matters only
+// where its count is not zero.
+//
+// The runtime takes bytes and plain pointers, so a non-contiguous type is a local matter of the
+// rank that has it: that rank packs its send side into a pooled device buffer (one PMPI_Pack per
+// non-empty block on the side that owns n blocks, pos running on) or receives packed and unpacks
+// the same way, and the collective itself moves packed bytes (as alltoall_derived does).
+// ---------------------------------------------------------------------------
+extern "C++" {
+static int copy_any(void *d, const void *s, size_t bytes) {
+    if (!bytes || d == s) return MPI_SUCCESS;
+    return is_dev(d) || is_dev(s) ? mv2h_memcpy_dtod(d, s, bytes) : (memcpy(d, s, bytes), 0);
+}
+
+static int side_checks(long count, MPI_Datatype dt) {
+    if (count < 0) return MPI_ERR_COUNT;
+    if (!dtype_valid(dt) || !dtype_committed(dt)) return MPI_ERR_TYPE;
+    return MPI_SUCCESS;
+}
+
+// The side of a call that owns n blocks: block j is cnt[j] elements of dt at buf + dsp[j] extents.
+// What the runtime sees of it is the user's buffer (contiguous type: bytes[j] at offs[j]) or, for
+// a non-contiguous type, a packed copy with the blocks back to back.
+struct NBlocks {
+    char *buf = nullptr;
+    MPI_Datatype dt = 0;
+    int n = 0;
+    std::vector<int> cnt, dsp;
+    bool packed = false;
+    void *tmp = nullptr;
+    std::vector<size_t> bytes, offs;
+    size_t total = 0;  // of the packed copy
+    char *rt_buf() const { return packed ? (char *)tmp : buf; }
+    ~NBlocks() {
+        if (tmp) pool_put(tmp);
+    }
+};
+
+// displs == nullptr: n blocks of counts[0] elements back to back (Gather / Scatter)
+static int nblocks_init(NBlocks &b, const void *buf, int n, const int *counts, const int *displs, MPI_Datatype dt) {
+    b.buf = (char *)buf;
+    b.dt = dt;
+    b.n = n;
+    b.cnt.resize(n), b.dsp.resize(n), b.bytes.resize(n), b.offs.resize(n);
+    b.packed = !dtype_is_contiguous(dt);
+    const size_t ext = b.packed ? 0 : (size_t)dtype_span(dt, 1), size = (size_t)dtype_size(dt);
+    for (int j = 0; j < n; ++j) {
+        b.cnt[j] = displs ? counts[j] : counts[0];
+        b.dsp[j] = displs ? (b.cnt[j] ? displs[j] : 0) : j * counts[0];
+        if (b.cnt[j] && b.dsp[j] < 0) return MPI_ERR_ARG;
+        b.bytes[j] = (size_t)b.cnt[j] * (b.packed ? size : ext);
+        b.offs[j] = b.packed ? b.total : (size_t)b.dsp[j] * ext;
+        b.total += b.packed ? b.bytes[j] : 0;
+    }
+    if (b.packed && b.total && !(b.tmp = pool_get(b.total))) return MPI_ERR_NO_MEM;
+    return MPI_SUCCESS;
+}
+
+static int nblocks_pack(NBlocks &b, MPI_Comm comm) {
+    int pos = 0, rc = MPI_SUCCESS;
+    const long ext = dtype_extent(b.dt);
+    for (int j = 0; j < b.n && !rc; ++j)
+        if (b.cnt[j]) rc = PMPI_Pack(b.buf + (long)b.dsp[j] * ext, b.cnt[j], b.dt, b.tmp, (int)b.total, &pos, comm);
+    return rc;
+}
+
+static int nblocks_unpack(NBlocks &b, int skip, MPI_Comm comm) {
+    int pos = 0, rc = MPI_SUCCESS;
+    const long ext = dtype_extent(b.dt);
+    for (int j = 0; j < b.n && !rc; ++j) {
+        if (!b.cnt[j]) continue;
+        if (j == skip) pos += (int)b.bytes[j];
+        else rc = PMPI_Unpack(b.tmp, (int)b.total, &pos, b.buf + (long)b.dsp[j] * ext, b.cnt[j], b.dt, comm);
+    }
+    return rc;
+}
+
+// One block of `count` elements of dt as the runtime reads (pack = true) or writes it: the
+// user's buffer, or a pooled packed copy for a non-contiguous type.
+struct OneBlock {
+    void *user = nullptr, *tmp = nullptr;
+    int count = 0;
+    MPI_Datatype dt = 0;
+    size_t bytes = 0;
+    void *rt_buf() const { return tmp ? tmp : user; }
+    ~OneBlock() {
+        if (tmp) pool_put(tmp);
+    }
+};
+static int oneblock_init(OneBlock &o, const void *buf, int count, MPI_Datatype dt, bool pack, MPI_Comm comm) {
+    o.user = (void *)buf;
+    o.count = count;
+    o.dt = dt;
+    if (dtype_is_contiguous(dt)) {
+        o.bytes = (size_t)dtype_span(dt, count);
+        return MPI_SUCCESS;
+    }
+    o.bytes = (size_t)dtype_size(dt) * (size_t)count;
+    if (!o.bytes) return MPI_SUCCESS;
+    if (!(o.tmp = pool_get(o.bytes))) return MPI_ERR_NO_MEM;
+    int pos = 0;
+    return pack ? PMPI_Pack(buf, count, dt, o.tmp, (int)o.bytes, &pos, comm) : MPI_SUCCESS;
+}
+
+// Allgatherv / Gather(v): my block goes out, the n-block side `rb` (nullptr where it is not
+// significant) comes in.  call(send, sbytes, recv, rbytes, roffs) is the runtime's collective.
+template <class Call>
+static int gather_like(const void *sendbuf, int sendcount, MPI_Datatype sendtype, NBlocks *rb, int me, MPI_Comm comm,
+                       Call call) {
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    OneBlock s;
+    int rc = MPI_SUCCESS;
+    if (in_place && rb->packed)  // my block out of the receive side, packed; in place no longer
+        rc = oneblock_init(s, rb->buf + (long)rb->dsp[me] * dtype_extent(rb->dt), rb->cnt[me], rb->dt, true, comm);
+    else if (in_place) s.user = MPI_IN_PLACE, s.bytes = rb->bytes[me];
+    else rc = oneblock_init(s, sendbuf, sendcount, sendtype, true, comm);
+    if (rc) return rc;
+    if (comm == MPI_COMM_SELF) {
+        if (s.rt_buf() != MPI_IN_PLACE) {
+            if (s.bytes != rb->bytes[0]) return MPI_ERR_TRUNCATE;
+            rc = copy_any(rb->rt_buf() + rb->offs[0], s.rt_buf(), s.bytes);
+        }
+    } else {
+        rc = call(s.rt_buf(), s.bytes, rb ? rb->rt_buf() : nullptr, rb ? rb->bytes.data() : nullptr,
+                  rb ? rb->offs.data() : nullptr);
+    }
+    if (!rc && rb && rb->packed && rb->total) rc = nblocks_unpack(*rb, in_place ? me : -1, comm);
+    return rc;
+}
+
+// Scatter(v): the n-block side `sb` (the root's) goes out, my block comes in.
+// call(send, sbytes, soffs, recv, rbytes) is the runtime's collective.
+template <class Call>
+static int scatter_like(NBlocks *sb, void *recvbuf, int recvcount, MPI_Datatype recvtype, MPI_Comm comm, Call call) {
+    const bool in_place = recvbuf == MPI_IN_PLACE;
+    int rc = MPI_SUCCESS;
+    if (sb && sb->packed && sb->total && (rc = nblocks_pack(*sb, comm))) return rc;
+    OneBlock r;
+    if (in_place) r.user = MPI_IN_PLACE;
+    else if ((rc = oneblock_init(r, recvbuf, recvcount, recvtype, false, comm))) return rc;
+    if (comm == MPI_COMM_SELF) {
+        if (!in_place) {
+            if (r.bytes != sb->bytes[0]) return MPI_ERR_TRUNCATE;
+            rc = copy_any(r.rt_buf(), sb->rt_buf() + sb->offs[0], r.bytes);
+        }
+    } else {
+        rc = call(sb ? sb->rt_buf() : nullptr, sb ? sb->bytes.data() : nullptr, sb ? sb->offs.data() : nullptr, r.rt_buf(),
+                  r.bytes);
+    }
+    if (!rc && r.tmp) {
+        int pos = 0;
+        rc = PMPI_Unpack(r.tmp, (int)r.bytes, &pos, recvbuf, recvcount, recvtype, comm);
+    }
+    return rc;
+}
+
+// comm, then root (MPI_ERR_ROOT); *n, *me: the communicator's size and this rank in it
+static int rooted_comm_checks(MPI_Comm comm, int root, int *n, int *me) {
+    if (!g_initialized || g_finalized) return MPI_ERR_OTHER;
+    if (comm_index(comm) < 0) return MPI_ERR_COMM;
+    *n = comm == MPI_COMM_SELF ? 1 : mv2h_size();
+    *me = comm_rank_of(comm);
+    const int csize = comm == MPI_COMM_SELF ? 1 : world().gsize;
+    if (root < 0 || root >= csize) return MPI_ERR_ROOT;
+    return MPI_SUCCESS;
+}
+
+static long sum_counts(const int *c, int n) {
+    long s = 0;
+    for (int j = 0; j < n; ++j) s += c[j];
+    return s;
+}
+
+}  // extern "C++"
+
+#define GS_FAIL(rc) return err_return(comm_index(comm) < 0 ? MPI_COMM_WORLD : comm, (rc), fn)
+
+int PMPI_Gather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                MPI_Datatype recvtype, int root, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Gather";
+    int n = 1, me = 0, rc;
+    if ((rc = rooted_comm_checks(comm, root, &n, &me))) GS_FAIL(rc);
+    const bool at_root = me == root, in_place = sendbuf == MPI_IN_PLACE;
+    if (in_place && !at_root) GS_FAIL(MPI_ERR_BUFFER);
+    if (!in_place) {
+        if ((rc = side_checks(sendcount, sendtype))) GS_FAIL(rc);
+        if (null_userbuf(sendbuf, sendcount, sendtype)) GS_FAIL(MPI_ERR_BUFFER);
+    }
+    NBlocks rb;
+    if (at_root) {
+        if ((rc = side_checks(recvcount, recvtype))) GS_FAIL(rc);
+        if (inplace_buf(recvbuf, recvcount) || null_userbuf(recvbuf, recvcount, recvtype)) GS_FAIL(MPI_ERR_BUFFER);
+        // gather.c:880-886: the send buffer is the root's own block of the receive buffer
+        if (!in_place && sendtype == recvtype && sendcount != 0 && recvcount != 0 &&
+            sendbuf == (const char *)recvbuf + (long)me * recvcount * dtype_size(recvtype))
+            GS_FAIL(MPI_ERR_BUFFER);
+        if ((rc = nblocks_init(rb, recvbuf, n, &recvcount, nullptr, recvtype))) GS_FAIL(rc);
+        if (!recvcount) return MPI_SUCCESS;
+    } else if (!sendcount || !dtype_size(sendtype)) {
+        return MPI_SUCCESS;
+    }
+    rc = gather_like(sendbuf, sendcount, sendtype, at_root ? &rb : nullptr, me, comm,
+                     [&](const void *s, size_t sbytes, void *r, const size_t *rbytes, const size_t *) {
+                         const size_t bytes = rbytes ? rbytes[me] : sbytes;
+                         if (rbytes && s != MPI_IN_PLACE && sbytes != bytes) return (int)MPI_ERR_TRUNCATE;
+                         return mv2h_gather(s, r, bytes, root, nullptr);
+                     });
+    return err_return(comm, rc, fn);
+}
+int MPI_Gather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+               MPI_Datatype recvtype, int root, MPI_Comm comm) WEAK(MPI_Gather);
+
+int PMPI_Gatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                 const int displs[], MPI_Datatype recvtype, int root, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Gatherv";
+    int n = 1, me = 0, rc;
+    if ((rc = rooted_comm_checks(comm, root, &n, &me))) GS_FAIL(rc);
+    const bool at_root = me == root, in_place = sendbuf == MPI_IN_PLACE;
+    if (in_place && !at_root) GS_FAIL(MPI_ERR_BUFFER);
+    if (!in_place) {
+        if ((rc = side_checks(sendcount, sendtype))) GS_FAIL(rc);
+        if (null_userbuf(sendbuf, sendcount, sendtype)) GS_FAIL(MPI_ERR_BUFFER);
+    }
+    NBlocks rb;
+    if (at_root) {
+        if (!recvcounts || !displs) GS_FAIL(MPI_ERR_ARG);
+        for (int j = 0; j < n; ++j)
+            if (recvcounts[j] < 0) GS_FAIL(MPI_ERR_COUNT);
+        if ((rc = side_checks(0, recvtype))) GS_FAIL(rc);
+        const long total = sum_counts(recvcounts, n);
+        if (inplace_buf(recvbuf, total) || null_userbuf(recvbuf, total, recvtype)) GS_FAIL(MPI_ERR_BUFFER);
+        if ((rc = nblocks_init(rb, recvbuf, n, recvcounts, displs, recvtype))) GS_FAIL(rc);
+    }
+    rc = gather_like(sendbuf, sendcount, sendtype, at_root ? &rb : nullptr, me, comm,
+                     [&](const void *s, size_t sbytes, void *r, const size_t *rbytes, const size_t *roffs) {
+                         return mv2h_gatherv(s, sbytes, r, rbytes, roffs, root, nullptr);
+                     });
+    return err_return(comm, rc, fn);
+}
+int MPI_Gatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                const int displs[], MPI_Datatype recvtype, int root, MPI_Comm comm) WEAK(MPI_Gatherv);
+
+int PMPI_Allgatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                    const int displs[], MPI_Datatype recvtype, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Allgatherv";
+    int n = 1, me = 0, rc;
+    if ((rc = rooted_comm_checks(comm, 0, &n, &me))) GS_FAIL(rc);
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    if (!recvcounts || !displs) GS_FAIL(MPI_ERR_ARG);
+    if (!in_place) {
+        if ((rc = side_checks(sendcount, sendtype))) GS_FAIL(rc);
+        if (null_userbuf(sendbuf, sendcount, sendtype)) GS_FAIL(MPI_ERR_BUFFER);
+    }
+    for (int j = 0; j < n; ++j)
+        if (recvcounts[j] < 0) GS_FAIL(MPI_ERR_COUNT);
+    if ((rc = side_checks(0, recvtype))) GS_FAIL(rc);
+    const long total = sum_counts(recvcounts, n);
+    if (inplace_buf(recvbuf, total) || null_userbuf(recvbuf, total, recvtype)) GS_FAIL(MPI_ERR_BUFFER);
+    // allgatherv.c:1118-1124: the send buffer is this rank's block of the receive buffer
+    if (!in_place && sendtype == recvtype && sendcount != 0 && recvcounts[me] != 0 &&
+        sendbuf == (const char *)recvbuf + (long)displs[me] * dtype_size(recvtype))
+        GS_FAIL(MPI_ERR_BUFFER);
+    NBlocks rb;
+    if ((rc = nblocks_init(rb, recvbuf, n, recvcounts, displs, recvtype))) GS_FAIL(rc);
+    rc = gather_like(sendbuf, sendcount, sendtype, &rb, me, comm,
+                     [&](const void *s, size_t sbytes, void *r, const size_t *rbytes, const size_t *roffs) {
+                         return mv2h_allgatherv(s, sbytes, r, rbytes, roffs, nullptr);
+                     });
+    return err_return(comm, rc, fn);
+}
+int MPI_Allgatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                   const int displs[], MPI_Datatype recvtype, MPI_Comm comm) WEAK(MPI_Allgatherv);
+
+int PMPI_Scatter(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                 MPI_Datatype recvtype, int root, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Scatter";
+    int n = 1, me = 0, rc;
+    if ((rc = rooted_comm_checks(comm, root, &n, &me))) GS_FAIL(rc);
+    const bool at_root = me == root, in_place = recvbuf == MPI_IN_PLACE;
+    if (in_place && !at_root) GS_FAIL(MPI_ERR_BUFFER);
+    NBlocks sb;
+    if (at_root) {
+        if ((rc = side_checks(sendcount, sendtype))) GS_FAIL(rc);
+        if (inplace_buf(sendbuf, sendcount) || null_userbuf(sendbuf, sendcount, sendtype)) GS_FAIL(MPI_ERR_BUFFER);
+    }
+    if (!in_place) {
+        if ((rc = side_checks(recvcount, recvtype))) GS_FAIL(rc);
+        if (null_userbuf(recvbuf, recvcount, recvtype)) GS_FAIL(MPI_ERR_BUFFER);
+    }
+    if (at_root) {
+        // scatter.c:790-796: the receive buffer is the root's own block of the send buffer
+        if (!in_place && sendtype == recvtype && sendcount != 0 && recvcount != 0 &&
+            recvbuf == (const char *)sendbuf + (long)me * sendcount * dtype_size(sendtype))
+            GS_FAIL(MPI_ERR_BUFFER);
+        if ((rc = nblocks_init(sb, sendbuf, n, &sendcount, nullptr, sendtype))) GS_FAIL(rc);
+        if (!sendcount) return MPI_SUCCESS;
+    } else if (!recvcount || !dtype_size(recvtype)) {
+        return MPI_SUCCESS;
+    }
+    rc = scatter_like(at_root ? &sb : nullptr, recvbuf, recvcount, recvtype, comm,
+                      [&](const void *s, const size_t *sbytes, const size_t *, void *r, size_t rbytes) {
+                          const size_t bytes = sbytes ? sbytes[me] : rbytes;
+                          if (sbytes && r != MPI_IN_PLACE && rbytes != bytes) return (int)MPI_ERR_TRUNCATE;
+                          return mv2h_scatter(s, r, bytes, root, nullptr);
+                      });
+    return err_return(comm, rc, fn);
+}
+int MPI_Scatter(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                MPI_Datatype recvtype, int root, MPI_Comm comm) WEAK(MPI_Scatter);
+
+int PMPI_Scatterv(const void *sendbuf, const int sendcounts[], const int displs[], MPI_Datatype sendtype, void *recvbuf,
+                  int recvcount, MPI_Datatype recvtype, int root, MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Scatterv";
+    int n = 1, me = 0, rc;
+    if ((rc = rooted_comm_checks(comm, root, &n, &me))) GS_FAIL(rc);
+    const bool at_root = me == root, in_place = recvbuf == MPI_IN_PLACE;
+    if (in_place && !at_root) GS_FAIL(MPI_ERR_BUFFER);
+    NBlocks sb;
+    if (at_root) {
+        if (!sendcounts || !displs) GS_FAIL(MPI_ERR_ARG);
+        for (int j = 0; j < n; ++j)
+            if (sendcounts[j] < 0) GS_FAIL(MPI_ERR_COUNT);
+        if ((rc = side_checks(0, sendtype))) GS_FAIL(rc);
+        const long total = sum_counts(sendcounts, n);
+        if (inplace_buf(sendbuf, total) || null_userbuf(sendbuf, total, sendtype)) GS_FAIL(MPI_ERR_BUFFER);
+    }
+    if (!in_place) {
+        if ((rc = side_checks(recvcount, recvtype))) GS_FAIL(rc);
+        if (null_userbuf(recvbuf, recvcount, recvtype)) GS_FAIL(MPI_ERR_BUFFER);
+    }
+    if (at_root && (rc = nblocks_init(sb, sendbuf, n, sendcounts, displs, sendtype))) GS_FAIL(rc);
+    rc = scatter_like(at_root ? &sb : nullptr, recvbuf, recvcount, recvtype, comm,
+                      [&](const void *s, const size_t *sbytes, const size_t *soffs, void *r, size_t rbytes) {
+                          return mv2h_scatterv(s, sbytes, soffs, r, rbytes, root, nullptr);
+                      });
+    return err_return(comm, rc, fn);
+}
+int MPI_Scatterv(const void *sendbuf, const int sendcounts[], const int displs[], MPI_Datatype sendtype, void *recvbuf,
+                 int recvcount, MPI_Datatype recvtype, int root, MPI_Comm comm) WEAK(MPI_Scatterv);
+#undef GS_FAIL
+
 int PMPI_Bcast(void *buffer, int count, MPI_Datatype dt, int root, MPI_Comm comm) {
     std::lock_guard<std::recursive_mutex> lk(g_cs);
     const char *fn = "MPI_Bcast";
@@ -1389,6 +1740,62 @@ int PMPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdisp
 int MPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype, void *recvbuf,
                    const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm,
                    MPI_Request *request) WEAK(MPI_Ialltoallv);
+
+// MPI_Igather(v) / MPI_Iscatter(v) / MPI_Iallgatherv: the blocking calls initiated with deferred
+// completion.  Igatherv's and Iscatterv's ranks meet on the host inside the initiation (the row
+// exchange), so starting them is not local.
+int PMPI_Igather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                 MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Igather", [&] {
+        return PMPI_Gather(sendbuf, sendcount, sendtype, recvbuf, recvcount, recvtype, root, comm);
+    });
+}
+int MPI_Igather(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request) WEAK(MPI_Igather);
+
+int PMPI_Igatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                  const int displs[], MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Igatherv", [&] {
+        return PMPI_Gatherv(sendbuf, sendcount, sendtype, recvbuf, recvcounts, displs, recvtype, root, comm);
+    });
+}
+int MPI_Igatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                 const int displs[], MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request)
+    WEAK(MPI_Igatherv);
+
+int PMPI_Iallgatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                     const int displs[], MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Iallgatherv", [&] {
+        return PMPI_Allgatherv(sendbuf, sendcount, sendtype, recvbuf, recvcounts, displs, recvtype, comm);
+    });
+}
+int MPI_Iallgatherv(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, const int recvcounts[],
+                    const int displs[], MPI_Datatype recvtype, MPI_Comm comm, MPI_Request *request)
+    WEAK(MPI_Iallgatherv);
+
+int PMPI_Iscatter(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                  MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Iscatter", [&] {
+        return PMPI_Scatter(sendbuf, sendcount, sendtype, recvbuf, recvcount, recvtype, root, comm);
+    });
+}
+int MPI_Iscatter(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
+                 MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request) WEAK(MPI_Iscatter);
+
+int PMPI_Iscatterv(const void *sendbuf, const int sendcounts[], const int displs[], MPI_Datatype sendtype, void *recvbuf,
+                   int recvcount, MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Iscatterv", [&] {
+        return PMPI_Scatterv(sendbuf, sendcounts, displs, sendtype, recvbuf, recvcount, recvtype, root, comm);
+    });
+}
+int MPI_Iscatterv(const void *sendbuf, const int sendcounts[], const int displs[], MPI_Datatype sendtype, void *recvbuf,
+                  int recvcount, MPI_Datatype recvtype, int root, MPI_Comm comm, MPI_Request *request)
+    WEAK(MPI_Iscatterv);
 
 int PMPI_Ibcast(void *buffer, int count, MPI_Datatype dt, int root, MPI_Comm comm, MPI_Request *request) {
     std::lock_guard<std::recursive_mutex> lk(g_cs);

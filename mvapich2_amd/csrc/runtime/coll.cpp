@@ -178,6 +178,7 @@ int mv2h_set_tuning(const char *key, long value) {
     else if (!strcmp(key, "light_release")) w.light_release = (int)value;
     else if (!strcmp(key, "withhold_done")) withhold_done((int)value);
     else if (!strcmp(key, "fake_split")) fake_split((int)value);
+    else if (!strcmp(key, "agv_via_a2a")) set_agv_via_a2a((int)value);
     else if (!strcmp(key, "oneshot_max")) {
         if ((size_t)value > w.slot_bytes && w.size > 1) return E_ARG;
         w.oneshot_max = (size_t)value;
@@ -212,6 +213,10 @@ int mv2h_get_info(const char *key, long *value) {
     else if (!strcmp(key, "a2a_oneshot_bytes")) *value = (long)a2a_path_calls(1);
     else if (!strcmp(key, "a2a_pipe")) *value = (long)a2a_path_calls(2);
     else if (!strcmp(key, "a2a_pipe_shift")) *value = (long)a2a_path_calls(3);
+    else if (!strcmp(key, "gv_oneshot_vec")) *value = (long)gv_path_calls(0);
+    else if (!strcmp(key, "gv_oneshot_bytes")) *value = (long)gv_path_calls(1);
+    else if (!strcmp(key, "gv_pipe")) *value = (long)gv_path_calls(2);
+    else if (!strcmp(key, "gv_pipe_shift")) *value = (long)gv_path_calls(3);
     else if (!strcmp(key, "call_allocs")) *value = (long)w.call_allocs;
     else if (!strcmp(key, "pool_trims")) *value = (long)w.pool_trims;
     else if (!strcmp(key, "rl_tiny_max")) *value = (long)w.rl_tiny_max;
@@ -570,6 +575,46 @@ int mv2h_alltoallv(const void *sendbuf, const size_t *sbytes, const size_t *soff
                    const size_t *roffs, void *stream) {
     if (int rc = alltoall_one_node_only("MPI_Alltoallv")) return rc;
     return alltoallv_node(sendbuf, sbytes, soffs, recvbuf, rbytes, roffs, stream);
+}
+
+// Several nodes: refused like the all-to-alls, from the job's shape alone.
+int mv2h_allgatherv(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes, const size_t *roffs,
+                    void *stream) {
+    if (int rc = alltoall_one_node_only("MPI_Allgatherv")) return rc;
+    return allgatherv_node(sendbuf, sbytes, recvbuf, rbytes, roffs, stream);
+}
+
+int mv2h_gather(const void *sendbuf, void *recvbuf, size_t bytes, int root, void *stream) {
+    if (int rc = alltoall_one_node_only("MPI_Gather")) return rc;
+    return gather_node(sendbuf, recvbuf, bytes, root, stream);
+}
+
+int mv2h_gatherv(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes, const size_t *roffs, int root,
+                 void *stream) {
+    if (int rc = alltoall_one_node_only("MPI_Gatherv")) return rc;
+    return gatherv_node(sendbuf, sbytes, recvbuf, rbytes, roffs, root, stream);
+}
+
+int mv2h_scatter(const void *sendbuf, void *recvbuf, size_t bytes, int root, void *stream) {
+    if (int rc = alltoall_one_node_only("MPI_Scatter")) return rc;
+    return scatter_node(sendbuf, recvbuf, bytes, root, stream);
+}
+
+int mv2h_scatterv(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, size_t rbytes, int root,
+                  void *stream) {
+    if (int rc = alltoall_one_node_only("MPI_Scatterv")) return rc;
+    return scatterv_node(sendbuf, sbytes, soffs, recvbuf, rbytes, root, stream);
+}
+
+int mv2h_gv_plan(int n, const size_t *len, int *path, int *grid, int *nrounds, size_t *maxlen) {
+    if (n < 1 || n > kMaxRanks || !len) return E_ARG;
+    A2APlan p{};
+    gv_plan(n, len, &p);
+    if (path) *path = p.path;
+    if (grid) *grid = p.grid;
+    if (nrounds) *nrounds = p.nrounds;
+    if (maxlen) *maxlen = p.maxlen;
+    return 0;
 }
 
 int mv2h_alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned char *aligned16, int *path,

@@ -57,6 +57,23 @@ int alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned
 // all-to-all calls by path (mv2h_get_info a2a_*): 0 one-shot vector, 1 one-shot byte-wise, 2 pipelined,
 // 3 those of the pipelined ones whose gather shifted at least one block
 uint64_t a2a_path_calls(int which);
+// MPI_Allgatherv / MPI_Gather(v) / MPI_Scatter(v) over this node's ranks, in bytes.  (void *)-1 is
+// MPI_IN_PLACE: the send buffer of Allgatherv and of Gather(v) at the root, the receive buffer of
+// Scatter(v) at the root.  Arguments that matter at the root only are not read elsewhere.
+int allgatherv_node(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes, const size_t *roffs,
+                    void *stream);
+int gather_node(const void *sendbuf, void *recvbuf, size_t bytes, int root, void *stream);
+int gatherv_node(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes, const size_t *roffs, int root,
+                 void *stream);
+int scatter_node(const void *sendbuf, void *recvbuf, size_t bytes, int root, void *stream);
+int scatterv_node(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, size_t rbytes, int root,
+                  void *stream);
+// The plan of one gather table (Allgatherv, Gather) from the n block lengths, which every rank
+// knows: the all-to-all's paths, never reading a displacement or an address.
+int gv_plan(int n, const size_t *len, A2APlan *out);
+// gather-table calls by path (mv2h_get_info gv_*), indexed like a2a_path_calls
+uint64_t gv_path_calls(int which);
+void set_agv_via_a2a(int on);  // test hook (mv2h_set_tuning "agv_via_a2a")
 
 // ---- coll_mn.cpp: the collectives of a job on several nodes ----
 int mn_allreduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *stream);

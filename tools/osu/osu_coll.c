@@ -6,19 +6,23 @@
  * report the average over ranks of per-rank mean latency), with `-d rocm`
  * device buffers and busbw columns added (OMB prints latency only).
  *
- *   osu_coll -c allreduce|reduce|scan|exscan|reduce_scatter|allgather|alltoall|alltoallv|bcast|reduce_local|
- *               latency|bw|all
+ *   osu_coll -c allreduce|reduce|scan|exscan|reduce_scatter|allgather|allgatherv|gather|scatter|alltoall|
+ *               alltoallv|bcast|reduce_local|latency|bw|all
  *            [-m min:max bytes] [-f size factor (2)] [-i iters] [-I large-message iters]
  *            [-x warmup] [-C cap bytes for -c all's reduce_scatter/allgather/bcast]
  *            [-d rocm|host] [-v (validate every collective)] [-j (JSON rows)]
+ *            [-T key=value (mv2h_set_tuning after MPI_Init, e.g. agv_via_a2a=1; may repeat)]
  * -c all runs allreduce over [min, max] and reduce_scatter, allgather, bcast over
  * [min, min(max, cap)] in one job (bench.py's N > 1 sweep: configs[2] and [3]), then the
  * device point-to-point latency and bandwidth between ranks 0 and 1 up to 16 MiB.
  * alltoall / alltoallv: the size is the bytes of one block (one pair); alltoallv runs the uniform
  * matrix, so its difference from alltoall is the host exchange of the counts.
+ * allgatherv / gather / scatter: the size is the bytes of one rank's block (root 0); allgatherv runs
+ * the uniform vector, so its difference from allgather is the kernel.
  */
 #include <hip/hip_runtime.h>
 #include <mpi.h>
+#include <mv2h.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -102,8 +106,10 @@ static int run_pt2pt(int rank, void *sbuf, void *rbuf, size_t lo, size_t hi) {
  * (i % 100 + 1) * (rank + 1); returns 1 when right */
 static int check(const char *c, const void *rbuf, size_t count, size_t sz, int rank, int size, const int *counts) {
     if (!strcmp(c, "reduce") || !strcmp(c, "reduce_local")) return 1;
-    const int a2a = !strcmp(c, "alltoall") || !strcmp(c, "alltoallv");
-    size_t n = !strcmp(c, "allgather") || a2a ? sz * (size_t)size : !strcmp(c, "bcast") ? sz : count * sizeof(float);
+    if (!strcmp(c, "gather") && rank != 0) return 1;
+    const int a2a = !strcmp(c, "alltoall") || !strcmp(c, "alltoallv"), sct = !strcmp(c, "scatter");
+    const int gat = !strcmp(c, "allgather") || !strcmp(c, "allgatherv") || !strcmp(c, "gather");
+    size_t n = gat || a2a ? sz * (size_t)size : !strcmp(c, "bcast") || sct ? sz : count * sizeof(float);
     if (!strcmp(c, "reduce_scatter")) n = (size_t)counts[rank] * sizeof(float);
     char *h = (char *)malloc(n ? n : 1);
     if (device) hipMemcpy(h, !strcmp(c, "bcast") ? rbuf : rbuf, n, hipMemcpyDeviceToHost);
@@ -125,12 +131,13 @@ static int check(const char *c, const void *rbuf, size_t count, size_t sz, int r
         for (size_t i = 0; i < (size_t)counts[rank] && ok; ++i) ok = f[i] == (float)((off + i) % 100 + 1) * tot;
     } else {
         /* allgather: block j = rank j's first sz bytes of its fill; bcast: rank 0's (bytes of floats);
-         * alltoall(v): block j = bytes [rank * sz, + sz) of rank j's fill */
-        const size_t span = a2a ? sz * (size_t)size : sz;
+         * alltoall(v): block j = bytes [rank * sz, + sz) of rank j's fill; allgatherv / gather (at the
+         * root): as allgather; scatter: bytes [rank * sz, + sz) of rank 0's fill */
+        const size_t span = a2a || sct ? sz * (size_t)size : sz;
         float *want = (float *)malloc((span / 4 + 1) * sizeof(float));
-        for (int j = 0; j < (!strcmp(c, "bcast") ? 1 : size) && ok; ++j) {
+        for (int j = 0; j < (!strcmp(c, "bcast") || sct ? 1 : size) && ok; ++j) {
             for (size_t i = 0; i < span / 4 + 1; ++i) want[i] = (float)((i % 100 + 1) * (j + 1));
-            ok = memcmp(h + (size_t)j * sz, (const char *)want + (a2a ? (size_t)rank * sz : 0), sz) == 0;
+            ok = memcmp(h + (size_t)j * sz, (const char *)want + (a2a || sct ? (size_t)rank * sz : 0), sz) == 0;
         }
         free(want);
     }
@@ -145,15 +152,16 @@ static int run_coll(const char *c, int rank, int size, void *sbuf, void *rbuf, s
     }
     int *counts = (int *)malloc(sizeof(int) * size);
     int *vcnt = (int *)malloc(sizeof(int) * size), *vdsp = (int *)malloc(sizeof(int) * size); /* alltoallv */
-    const int a2a = !strcmp(c, "alltoall") || !strcmp(c, "alltoallv");
+    const int a2a = !strcmp(c, "alltoall") || !strcmp(c, "alltoallv"), sct = !strcmp(c, "scatter");
+    const int agv = !strcmp(c, "allgatherv"), gat = agv || !strcmp(c, "allgather") || !strcmp(c, "gather");
     int bad_any = 0;
     for (size_t sz = lo; sz <= hi; sz *= factor) {
         const size_t count = sz / sizeof(float) ? sz / sizeof(float) : 1;
         const int large = count > 8192; /* osu_allreduce.c:101 */
         const int iters = large ? iters_large : iters_small, skip = large ? skip_large : skip_small;
         /* the fill covers what allgather / bcast send (sz bytes) and the reducing operands */
-        fill(sbuf, a2a ? (sz * (size_t)size + 3) / 4 : (sz + 3) / 4 > count ? (sz + 3) / 4 : count, rank);
-        for (int r = 0; a2a && r < size; ++r) vcnt[r] = (int)sz, vdsp[r] = (int)((size_t)r * sz);
+        fill(sbuf, a2a || sct ? (sz * (size_t)size + 3) / 4 : (sz + 3) / 4 > count ? (sz + 3) / 4 : count, rank);
+        for (int r = 0; (a2a || agv) && r < size; ++r) vcnt[r] = (int)sz, vdsp[r] = (int)((size_t)r * sz);
         if (!strcmp(c, "bcast") && rank != 0) {
             if (device) hipMemset(sbuf, 0xA5, sz);
             else memset(sbuf, 0xA5, sz);
@@ -175,6 +183,9 @@ static int run_coll(const char *c, int rank, int size, void *sbuf, void *rbuf, s
             /* osu_reduce_scatter.c:116-131: size/n each, first size%n ranks one more */
             else if (!strcmp(c, "reduce_scatter")) rc |= MPI_Reduce_scatter(sbuf, rbuf, counts, MPI_FLOAT, MPI_SUM, MPI_COMM_WORLD);
             else if (!strcmp(c, "allgather")) rc |= MPI_Allgather(sbuf, (int)sz, MPI_CHAR, rbuf, (int)sz, MPI_CHAR, MPI_COMM_WORLD);
+            else if (agv) rc |= MPI_Allgatherv(sbuf, (int)sz, MPI_CHAR, rbuf, vcnt, vdsp, MPI_CHAR, MPI_COMM_WORLD);
+            else if (!strcmp(c, "gather")) rc |= MPI_Gather(sbuf, (int)sz, MPI_CHAR, rbuf, (int)sz, MPI_CHAR, 0, MPI_COMM_WORLD);
+            else if (sct) rc |= MPI_Scatter(sbuf, (int)sz, MPI_CHAR, rbuf, (int)sz, MPI_CHAR, 0, MPI_COMM_WORLD);
             else if (!strcmp(c, "alltoall")) rc |= MPI_Alltoall(sbuf, (int)sz, MPI_CHAR, rbuf, (int)sz, MPI_CHAR, MPI_COMM_WORLD);
             else if (!strcmp(c, "alltoallv"))
                 rc |= MPI_Alltoallv(sbuf, vcnt, vdsp, MPI_CHAR, rbuf, vcnt, vdsp, MPI_CHAR, MPI_COMM_WORLD);
@@ -194,8 +205,8 @@ static int run_coll(const char *c, int rank, int size, void *sbuf, void *rbuf, s
         double algbw = sz / (sum * 1e-6) / 1e9;
         double bf = 1.0;
         if (!strcmp(c, "allreduce")) bf = 2.0 * (size - 1) / size;
-        else if (!strcmp(c, "reduce_scatter") || !strcmp(c, "allgather") || a2a) bf = (double)(size - 1) / size;
-        if (!strcmp(c, "allgather") || a2a) algbw *= size;
+        else if (!strcmp(c, "reduce_scatter") || gat || sct || a2a) bf = (double)(size - 1) / size;
+        if (gat || sct || a2a) algbw *= size;
         if (!strcmp(c, "reduce_local")) { bf = 3.0; }
         bad_any |= rc || (validate && !valid);
         if (rank == 0 && json)
@@ -238,9 +249,20 @@ static int osu_run(int argc, char **argv, int init) {
         else if (!strcmp(argv[i], "-C") && i + 1 < argc) cap_sz = strtoull(argv[++i], NULL, 10);
         else if (!strcmp(argv[i], "-j")) json = 1;
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) jpath = argv[++i];
+        else if (!strcmp(argv[i], "-T") && i + 1 < argc && strchr(argv[i + 1], '=')) ++i; /* applied after MPI_Init */
         else { fprintf(stderr, "osu_coll: unknown argument %s\n", argv[i]); return 2; }
     }
     if (init) MPI_Init(&argc, &argv);
+    for (int i = 1; i + 1 < argc; ++i) {
+        if (strcmp(argv[i], "-T")) continue;
+        char key[64];
+        const char *eq = strchr(argv[++i], '=');
+        snprintf(key, sizeof key, "%.*s", (int)(eq - argv[i]), argv[i]);
+        if (mv2h_set_tuning(key, atol(eq + 1))) {
+            fprintf(stderr, "osu_coll: mv2h_set_tuning refuses %s\n", argv[i]);
+            return 2;
+        }
+    }
     int rank, size;
     MPI_Comm_rank(MPI_COMM_WORLD, &rank);
     MPI_Comm_size(MPI_COMM_WORLD, &size);
@@ -249,7 +271,8 @@ static int osu_run(int argc, char **argv, int init) {
         fprintf(stderr, "osu_coll: cannot write %s\n", jpath);
         jout = stdout;
     }
-    if ((!strcmp(coll, "alltoall") || !strcmp(coll, "alltoallv")) && max_sz * (size_t)size > 0x7fffffff) {
+    if ((!strcmp(coll, "alltoall") || !strcmp(coll, "alltoallv") || !strcmp(coll, "allgatherv")) &&
+        max_sz * (size_t)size > 0x7fffffff) {
         fprintf(stderr, "osu_coll: -c %s blocks of %zu bytes overflow int displacements at %d ranks\n", coll, max_sz, size);
         MPI_Abort(MPI_COMM_WORLD, 1);
     }
