@@ -195,6 +195,25 @@ int mv2h_unpack_strided(const void *src, void *dst, size_t nblocks, size_t blk_b
 int mv2h_pack_segments(const void *src, void *dst, size_t count, size_t extent,
                        const int64_t *offs, const int64_t *lens, int nseg, int unpack,
                        void *stream);
+/* Up to 8 blocks with a layout each, in one launch (the n blocks of one side of MPI_Alltoallw).
+ * Block b is count[b] elements extent[b] bytes apart whose element 0 starts at base + disp[b]
+ * (signed: a negative lower bound goes into it); one element is the byte segments
+ * [seg_first[b], seg_first[b + 1]) of offs / lens in pack order; its packed form starts at
+ * packed + packed_off[b].  Per block the semantics are mv2h_pack_segments': unpack != 0 writes the
+ * segments' bytes of base from packed and nothing else.  A block with count 0 or no segment is
+ * empty and its other numbers are not read; nothing is launched when every block is empty.
+ * MPI_ERR_ARG's class, with nothing launched, for nblk > 8, a non-positive segment length or a
+ * negative segment offset.  mv2h_get_info keys: "pack_blocks_calls" counts launches,
+ * "pack_blocks_global_tab" those in which some block's folded run table exceeded the 512 runs
+ * staged in LDS.  mv2h_set_tuning("pack_blocks", 0) makes the MPI layer pack block by block. */
+int mv2h_pack_blocks(void *base, void *packed, int nblk, const int64_t *disp, const size_t *count,
+                     const size_t *extent, const size_t *packed_off, const int *seg_first,
+                     const int64_t *offs, const int64_t *lens, int unpack, void *stream);
+/* Test hook (host only: no GPU needed): the workgroups mv2h_pack_blocks deals to n blocks of
+ * units[b] packed units under a grid cap of max_grid (<= 0: the "max_grid" tuning): block b gets
+ * [wg0[b], wg0[b] + nwg[b]); *grid is their sum, *tile the units one workgroup moves per stride. */
+int mv2h_pack_blocks_plan(int n, const size_t *units, long max_grid, int *wg0, int *nwg, int *grid,
+                          size_t *tile);
 
 /* ---- reduction-order plans (host only: no GPU needed) ----
  * The algorithm MVAPICH2 2.3.7 selects for a one-node collective and the

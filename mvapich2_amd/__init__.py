@@ -75,6 +75,11 @@ def lib():
         "mv2h_unpack_strided": ([c_vp, c_vp, c_sz, c_sz, c_sz, c_vp], c_int),
         "mv2h_pack_segments": ([c_vp, c_vp, c_sz, c_sz, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                 c_int, c_int, c_vp], c_int),
+        "mv2h_pack_blocks": ([c_vp, c_vp, c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_sz), ctypes.POINTER(c_sz),
+                              ctypes.POINTER(c_sz), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_int64),
+                              ctypes.POINTER(ctypes.c_int64), c_int, c_vp], c_int),
+        "mv2h_pack_blocks_plan": ([c_int, ctypes.POINTER(c_sz), ctypes.c_long, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                   ctypes.POINTER(c_int), ctypes.POINTER(c_sz)], c_int),
         "mv2h_init": ([], c_int),
         "mv2h_finalize": ([], c_int),
         "mv2h_rank": ([], c_int),
@@ -117,6 +122,8 @@ def lib():
         "MPI_Alltoall": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int], c_int),
         "MPI_Alltoallv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, ctypes.POINTER(c_int),
                            ctypes.POINTER(c_int), c_int, c_int], c_int),
+        "MPI_Alltoallw": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp,
+                           ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int], c_int),
         "MPI_Gather": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int], c_int),
         "MPI_Gatherv": ([c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_int], c_int),
         "MPI_Scatter": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int], c_int),
@@ -156,6 +163,9 @@ def lib():
         "MPI_Ialltoall": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Ialltoallv": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_vp, ctypes.POINTER(c_int),
                             ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int)], c_int),
+        "MPI_Ialltoallw": ([c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp,
+                            ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
+                            ctypes.POINTER(c_int)], c_int),
         "MPI_Igather": ([c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
         "MPI_Igatherv": ([c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_int,
                           ctypes.POINTER(c_int)], c_int),
@@ -283,6 +293,33 @@ def alltoallv_plan(slen, rlen=None, aligned16=None):
     return rc, A2A_PATHS[path.value], grid.value, rounds.value, maxlen.value
 
 
+def pack_blocks(base, packed, blocks, unpack=False):
+    """One launch over up to 8 blocks (mv2h_pack_blocks).  base / packed: device addresses; blocks:
+    [(disp, count, extent, packed_off, [(off, len), ...]), ...] in bytes."""
+    n = len(blocks)
+    i64 = lambda v: (ctypes.c_int64 * max(len(v), 1))(*v)  # noqa: E731
+    sz = lambda v: (ctypes.c_size_t * max(len(v), 1))(*v)  # noqa: E731
+    first, offs, lens = [0], [], []
+    for b in blocks:
+        offs += [o for o, _ in b[4]]
+        lens += [ln for _, ln in b[4]]
+        first.append(len(offs))
+    return lib().mv2h_pack_blocks(base, packed, n, i64([b[0] for b in blocks]), sz([b[1] for b in blocks]),
+                                  sz([b[2] for b in blocks]), sz([b[3] for b in blocks]), (ctypes.c_int * (n + 1))(*first),
+                                  i64(offs), i64(lens), int(unpack), None)
+
+
+def pack_blocks_plan(units, max_grid=0):
+    """(rc, wg0, nwg, grid, tile): the workgroups mv2h_pack_blocks deals to blocks of units[b] packed
+    units under a cap of max_grid (0: the max_grid tuning).  Host only."""
+    n = len(units)
+    wg0, nwg = (ctypes.c_int * max(n, 1))(), (ctypes.c_int * max(n, 1))()
+    grid, tile = ctypes.c_int(), ctypes.c_size_t()
+    rc = lib().mv2h_pack_blocks_plan(n, (ctypes.c_size_t * max(n, 1))(*units), max_grid, wg0, nwg, ctypes.byref(grid),
+                                     ctypes.byref(tile))
+    return rc, list(wg0)[:n], list(nwg)[:n], grid.value, tile.value
+
+
 def _sz(v):
     return (ctypes.c_size_t * len(v))(*v) if v is not None else None
 
@@ -329,7 +366,7 @@ def gv_plan(lens):
 
 
 __all__ = ["lib", "check", "DeviceBuffer", "MPIError", "reduce_local", "alltoall", "alltoallv", "alltoallv_plan",
-           "allgatherv", "gather", "gatherv", "scatter", "scatterv", "gv_plan",
+           "allgatherv", "gather", "gatherv", "scatter", "scatterv", "gv_plan", "pack_blocks", "pack_blocks_plan",
            "np_dtype", "consts", "OPS", "TYPES"]
 
 

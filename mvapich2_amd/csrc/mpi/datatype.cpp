@@ -348,6 +348,18 @@ int dtype_unpack(const void *in, int count, MPI_Datatype dt, void *out) {
     return count > 0 ? pack_impl((const char *)in, count, dt, (char *)out, true) : MPI_SUCCESS;
 }
 
+bool dtype_flat(MPI_Datatype dt, std::vector<int64_t> &offs, std::vector<int64_t> &lens) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::vector<Seg> segs;
+    long ext = 0, size = 0;
+    if (!type_segs(dt, segs, ext, size)) return false;
+    for (const Seg &s : segs) {
+        offs.push_back(s.off);
+        lens.push_back(s.len);
+    }
+    return true;
+}
+
 long dtype_span(MPI_Datatype dt, int count) {
     if (count <= 0) return 0;
     if (const mv2::DtypeInfo *b = mv2::dtype_lookup(dt)) return (long)count * b->extent;

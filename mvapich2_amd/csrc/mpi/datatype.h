@@ -1,5 +1,9 @@
 // datatype.h — builtin + derived datatype queries used by the MPI glue.
 #pragma once
+#include <stdint.h>
+
+#include <vector>
+
 #include "../../../include/mpi.h"
 
 bool dtype_valid(MPI_Datatype dt);
@@ -19,3 +23,6 @@ void dtype_merge_typemap(char *dst, const char *src, MPI_Datatype dt, long count
 // on the packed size); either side may be device or host memory, device work is synchronous
 int dtype_pack(const void *in, int count, MPI_Datatype dt, void *out);
 int dtype_unpack(const void *in, int count, MPI_Datatype dt, void *out);
+// appends the byte segments of one element in pack order (offsets from the buffer pointer, as
+// MPI_Pack reads them) to offs / lens; false: not a datatype
+bool dtype_flat(MPI_Datatype dt, std::vector<int64_t> &offs, std::vector<int64_t> &lens);

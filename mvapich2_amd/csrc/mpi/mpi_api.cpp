@@ -857,9 +857,145 @@ int PMPI_Alltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, voi
 int MPI_Alltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void *recvbuf, int recvcount,
                  MPI_Datatype recvtype, MPI_Comm comm) WEAK(MPI_Alltoall);
 
-// Contiguous types only: a non-contiguous type on either side is refused with
-// MPI_ERR_UNSUPPORTED_OPERATION (packing per pair is not built).  Counts and displacements are in
-// elements of their side's type, as in the reference; the runtime takes bytes.
+// ---------------------------------------------------------------------------
+// MPI_Alltoallw, and MPI_Alltoallv with a non-contiguous type (alltoallw.c:425-530 for the checks).
+// A side of the call -- n blocks, block j = cnt[j] elements of dt[j] at buf + dsp[j] bytes -- is
+// either left alone or staged.  Every type of a non-empty block contiguous: the runtime reads or
+// writes the user's buffer at the byte displacements (all-contiguous Alltoallw is Alltoallv with
+// byte displacements).  Otherwise the whole side goes through one pooled device buffer in which
+// block j is packed at a 16-byte-aligned running offset, cnt[j] x size(dt[j]) bytes long, so the
+// exchange sees aligned blocks and never shifts.  A device buffer is staged by ONE launch for all
+// n blocks (mv2h_pack_blocks, pack/pack_blocks.hip); a host buffer, or any buffer under
+// mv2h_set_tuning("pack_blocks", 0), block by block (dtype_pack / dtype_unpack).  The exchange is
+// mv2h_alltoallv on what the two sides show: a pair whose packed lengths differ is
+// MPI_ERR_TRUNCATE on every rank before it, and the receive side is then not written.
+// ---------------------------------------------------------------------------
+extern "C++" {
+struct WSide {
+    char *buf = nullptr;
+    int n = 0;
+    std::vector<int> cnt;
+    std::vector<long> dsp;  // bytes
+    std::vector<MPI_Datatype> dt;
+    bool staged = false;
+    void *tmp = nullptr;
+    std::vector<size_t> bytes, offs;  // what the runtime sees
+    size_t total = 0;                 // of the staging buffer
+    char *rt_buf() const { return staged ? (char *)tmp : buf; }
+    ~WSide() {
+        if (tmp) pool_put(tmp);
+    }
+};
+
+// one element is its extent's bytes and nothing else (a builtin pair type has padding)
+static bool plain_type(MPI_Datatype dt) {
+    return dtype_is_contiguous(dt) && dtype_size(dt) == dtype_extent(dt) && dtype_true_lb(dt) == 0;
+}
+
+static void wside_set(WSide &s, const void *buf, int n, const int *counts, const int *displs, const MPI_Datatype *types,
+                      MPI_Datatype one) {
+    s.buf = (char *)buf;
+    s.n = n;
+    s.cnt.assign(counts, counts + n);
+    s.dsp.resize(n), s.dt.resize(n);
+    for (int j = 0; j < n; ++j) {
+        s.dt[j] = types ? types[j] : one;
+        // Alltoallw: bytes; Alltoallv: extents of the side's one type
+        s.dsp[j] = !s.cnt[j] ? 0 : (types ? (long)displs[j] : (long)displs[j] * dtype_extent(one));
+    }
+}
+
+// the runtime's view of the side; a staged side gets its buffer here
+static int wside_plan(WSide &s) {
+    s.bytes.assign(s.n, 0), s.offs.assign(s.n, 0);
+    s.staged = false, s.total = 0;
+    for (int j = 0; j < s.n; ++j) s.staged = s.staged || (s.cnt[j] && !plain_type(s.dt[j]));
+    for (int j = 0; j < s.n; ++j) {
+        if (!s.cnt[j]) continue;
+        s.bytes[j] = (size_t)s.cnt[j] * (size_t)dtype_size(s.dt[j]);  // a zero-size type: as count 0
+        s.offs[j] = s.staged ? s.total : (size_t)s.dsp[j];
+        if (s.staged) s.total += (s.bytes[j] + 15) & ~(size_t)15;
+    }
+    if (s.staged && s.total && !(s.tmp = pool_get(s.total))) return MPI_ERR_NO_MEM;
+    return MPI_SUCCESS;
+}
+
+// pack the user's blocks into the staging buffer, or unpack them out of it (gap bytes keep
+// their value)
+static int wside_move(WSide &s, bool unpack) {
+    if (!s.staged || !s.total) return MPI_SUCCESS;
+    long batched = 0;
+    mv2h_get_info("pack_blocks", &batched);
+    if (batched && s.n <= kMaxRanks && is_dev(s.buf)) {
+        int64_t disp[kMaxRanks] = {};
+        size_t count[kMaxRanks] = {}, extent[kMaxRanks] = {}, poff[kMaxRanks] = {};
+        int first[kMaxRanks + 1];
+        std::vector<int64_t> offs, lens;
+        for (int j = 0; j < s.n; ++j) {
+            first[j] = (int)offs.size();
+            if (!s.bytes[j]) continue;  // an empty block: no segment
+            disp[j] = s.dsp[j];
+            poff[j] = s.offs[j];
+            if (plain_type(s.dt[j])) {  // one element of the block's bytes
+                count[j] = 1;
+                extent[j] = s.bytes[j];
+                offs.push_back(0), lens.push_back((int64_t)s.bytes[j]);
+            } else {
+                count[j] = (size_t)s.cnt[j];
+                extent[j] = (size_t)dtype_extent(s.dt[j]);
+                if (!dtype_flat(s.dt[j], offs, lens)) return MPI_ERR_TYPE;
+            }
+        }
+        first[s.n] = (int)offs.size();
+        return mv2h_pack_blocks(s.buf, s.tmp, s.n, disp, count, extent, poff, first, offs.data(), lens.data(), unpack,
+                                nullptr);
+    }
+    int rc = MPI_SUCCESS;
+    for (int j = 0; j < s.n && !rc; ++j) {
+        if (!s.bytes[j]) continue;
+        char *user = s.buf + s.dsp[j], *packed = (char *)s.tmp + s.offs[j];
+        rc = unpack ? dtype_unpack(packed, s.cnt[j], s.dt[j], user) : dtype_pack(user, s.cnt[j], s.dt[j], packed);
+    }
+    return rc;
+}
+
+// Several nodes: refused like MPI_Alltoallv, here before any pack work.
+static int a2aw_one_node_only(MPI_Comm comm, const char *fn) {
+    long nnodes = 1;
+    if (comm == MPI_COMM_SELF || mv2h_get_info("nnodes", &nnodes) || nnodes <= 1) return MPI_SUCCESS;
+    MV2_ERR("%s: only jobs on one node are supported (this job spans %ld nodes)", fn, nnodes);
+    return MPI_ERR_OTHER;
+}
+
+// S and R hold the blocks (wside_set); in place S is not read and the blocks leave from R's.
+static int a2aw_run(WSide &S, WSide &R, bool in_place, MPI_Comm comm) {
+    int rc = wside_plan(R);
+    if (rc) return rc;
+    if (in_place && !R.staged) {
+        if (comm == MPI_COMM_SELF) return MPI_SUCCESS;
+        return mv2h_alltoallv(MPI_IN_PLACE, nullptr, nullptr, R.buf, R.bytes.data(), R.offs.data(), nullptr);
+    }
+    if (in_place) {
+        // a non-contiguous receive side: its blocks are packed into a send staging buffer, the
+        // exchange fills a second one, and that is unpacked over them
+        if (comm == MPI_COMM_SELF) return MPI_SUCCESS;
+        S.buf = R.buf, S.n = R.n, S.cnt = R.cnt, S.dsp = R.dsp, S.dt = R.dt;
+    }
+    if ((rc = wside_plan(S)) || (rc = wside_move(S, false))) return rc;
+    if (comm == MPI_COMM_SELF) {
+        if (S.bytes[0] != R.bytes[0]) return MPI_ERR_TRUNCATE;
+        void *d = R.rt_buf() + R.offs[0];
+        const void *s = S.rt_buf() + S.offs[0];
+        if (R.bytes[0]) rc = is_dev(d) || is_dev(s) ? mv2h_memcpy_dtod(d, s, R.bytes[0]) : (memcpy(d, s, R.bytes[0]), 0);
+    } else {
+        rc = mv2h_alltoallv(S.rt_buf(), S.bytes.data(), S.offs.data(), R.rt_buf(), R.bytes.data(), R.offs.data(), nullptr);
+    }
+    return rc ? rc : wside_move(R, true);
+}
+}  // extern "C++"
+
+// Counts and displacements are in elements (extents) of their side's type, as in the reference; the
+// runtime takes bytes.  A non-contiguous type on either side goes the way of MPI_Alltoallw above.
 int PMPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype,
                    void *recvbuf, const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm) {
     std::lock_guard<std::recursive_mutex> lk(g_cs);
@@ -881,8 +1017,14 @@ int PMPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispl
     if (inplace_buf(recvbuf, rtotal) || null_userbuf(recvbuf, rtotal, recvtype)) return err_return(comm, MPI_ERR_BUFFER, fn);
     if (!in_place && stotal && rtotal && sendbuf == recvbuf) return err_return(comm, MPI_ERR_BUFFER, fn);
     if (!dtype_is_contiguous(recvtype) || (!in_place && !dtype_is_contiguous(sendtype))) {
-        MV2_ERR("%s: non-contiguous datatypes are not supported", fn);
-        return err_return(comm, MPI_ERR_UNSUPPORTED_OPERATION, fn);
+        for (int j = 0; j < n; ++j)
+            if ((recvcounts[j] && rdispls[j] < 0) || (!in_place && sendcounts[j] && sdispls[j] < 0))
+                return err_return(comm, MPI_ERR_ARG, fn);
+        if (const int rc = a2aw_one_node_only(comm, fn)) return err_return(comm, rc, fn);
+        WSide S, R;
+        wside_set(R, recvbuf, n, recvcounts, rdispls, nullptr, recvtype);
+        if (!in_place) wside_set(S, sendbuf, n, sendcounts, sdispls, nullptr, sendtype);
+        return err_return(comm, a2aw_run(S, R, in_place, comm), fn);
     }
     const size_t rext = (size_t)dtype_span(recvtype, 1), sext = in_place ? rext : (size_t)dtype_span(sendtype, 1);
     std::vector<size_t> sb(n), so(n), rb(n), ro(n);
@@ -909,6 +1051,52 @@ int PMPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispl
 }
 int MPI_Alltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype, void *recvbuf,
                   const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm) WEAK(MPI_Alltoallv);
+
+// Checks in MPI_Alltoallv's order here: communicator, arrays, then per block count, type and
+// committed (a type matters only where its count is not zero, alltoallw.c:483-507), the buffers
+// (:509-521), the alias check (:474-475).  MPI_IN_PLACE takes counts, displacements and types from
+// the receive side.  Displacements are bytes; one matters only where its count is not zero.
+int PMPI_Alltoallw(const void *sendbuf, const int sendcounts[], const int sdispls[], const MPI_Datatype sendtypes[],
+                   void *recvbuf, const int recvcounts[], const int rdispls[], const MPI_Datatype recvtypes[],
+                   MPI_Comm comm) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    const char *fn = "MPI_Alltoallw";
+    if (!g_initialized || g_finalized) return err_return(comm, MPI_ERR_OTHER, fn);
+    if (comm_index(comm) < 0) return err_return(MPI_COMM_WORLD, MPI_ERR_COMM, fn);
+    const bool in_place = sendbuf == MPI_IN_PLACE;
+    if (!recvcounts || !rdispls || !recvtypes || (!in_place && (!sendcounts || !sdispls || !sendtypes)))
+        return err_return(comm, MPI_ERR_ARG, fn);
+    const int n = comm == MPI_COMM_SELF ? 1 : mv2h_size();
+    int s1 = -1, r1 = -1;  // the first non-empty block of each side
+    for (int j = 0; j < n; ++j) {
+        if (!in_place) {
+            if (sendcounts[j] < 0) return err_return(comm, MPI_ERR_COUNT, fn);
+            if (sendcounts[j] > 0 && (!dtype_valid(sendtypes[j]) || !dtype_committed(sendtypes[j])))
+                return err_return(comm, MPI_ERR_TYPE, fn);
+            if (sendcounts[j] > 0 && s1 < 0) s1 = j;
+        }
+        if (recvcounts[j] < 0) return err_return(comm, MPI_ERR_COUNT, fn);
+        if (recvcounts[j] > 0 && (!dtype_valid(recvtypes[j]) || !dtype_committed(recvtypes[j])))
+            return err_return(comm, MPI_ERR_TYPE, fn);
+        if (recvcounts[j] > 0 && r1 < 0) r1 = j;
+    }
+    if (s1 >= 0 && null_userbuf(sendbuf, sendcounts[s1], sendtypes[s1])) return err_return(comm, MPI_ERR_BUFFER, fn);
+    if (r1 >= 0 && (inplace_buf(recvbuf, recvcounts[r1]) || null_userbuf(recvbuf, recvcounts[r1], recvtypes[r1])))
+        return err_return(comm, MPI_ERR_BUFFER, fn);
+    if (!in_place && sendcounts == recvcounts && sendtypes == recvtypes && sendbuf == recvbuf)
+        return err_return(comm, MPI_ERR_BUFFER, fn);
+    for (int j = 0; j < n; ++j)
+        if ((recvcounts[j] && rdispls[j] < 0) || (!in_place && sendcounts[j] && sdispls[j] < 0))
+            return err_return(comm, MPI_ERR_ARG, fn);
+    if (const int rc = a2aw_one_node_only(comm, fn)) return err_return(comm, rc, fn);
+    WSide S, R;
+    wside_set(R, recvbuf, n, recvcounts, rdispls, recvtypes, MPI_DATATYPE_NULL);
+    if (!in_place) wside_set(S, sendbuf, n, sendcounts, sdispls, sendtypes, MPI_DATATYPE_NULL);
+    return err_return(comm, a2aw_run(S, R, in_place, comm), fn);
+}
+int MPI_Alltoallw(const void *sendbuf, const int sendcounts[], const int sdispls[], const MPI_Datatype sendtypes[],
+                  void *recvbuf, const int recvcounts[], const int rdispls[], const MPI_Datatype recvtypes[],
+                  MPI_Comm comm) WEAK(MPI_Alltoallw);
 
 // ---------------------------------------------------------------------------
 // MPI_Gather(v) / MPI_Scatter(v) / MPI_Allgatherv.  Checks after gather.c:823-905, gatherv.c:
@@ -1740,6 +1928,20 @@ int PMPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdisp
 int MPI_Ialltoallv(const void *sendbuf, const int sendcounts[], const int sdispls[], MPI_Datatype sendtype, void *recvbuf,
                    const int recvcounts[], const int rdispls[], MPI_Datatype recvtype, MPI_Comm comm,
                    MPI_Request *request) WEAK(MPI_Ialltoallv);
+
+// As MPI_Ialltoallv: the counts are exchanged on the host at initiation, which is therefore not
+// local; packing, exchange and unpacking run behind the request.
+int PMPI_Ialltoallw(const void *sendbuf, const int sendcounts[], const int sdispls[], const MPI_Datatype sendtypes[],
+                    void *recvbuf, const int recvcounts[], const int rdispls[], const MPI_Datatype recvtypes[],
+                    MPI_Comm comm, MPI_Request *request) {
+    std::lock_guard<std::recursive_mutex> lk(g_cs);
+    return start_coll(request, "MPI_Ialltoallw", [&] {
+        return PMPI_Alltoallw(sendbuf, sendcounts, sdispls, sendtypes, recvbuf, recvcounts, rdispls, recvtypes, comm);
+    });
+}
+int MPI_Ialltoallw(const void *sendbuf, const int sendcounts[], const int sdispls[], const MPI_Datatype sendtypes[],
+                   void *recvbuf, const int recvcounts[], const int rdispls[], const MPI_Datatype recvtypes[],
+                   MPI_Comm comm, MPI_Request *request) WEAK(MPI_Ialltoallw);
 
 // MPI_Igather(v) / MPI_Iscatter(v) / MPI_Iallgatherv: the blocking calls initiated with deferred
 // completion.  Igatherv's and Iscatterv's ranks meet on the host inside the initiation (the row

@@ -21,6 +21,7 @@
 
 #include "../coll/kernels.h"
 #include "../common.h"
+#include "pack_runs.h"
 
 namespace mv2 {
 
@@ -117,48 +118,10 @@ __global__ __launch_bounds__(kThreads) void k_pack_lds(const char *__restrict__ 
 // device copies of MPID_Segment_pack_device (ibv_cuda_util.c:37-49, :623).
 // The run table is staged in LDS when it fits; the packed side is read /
 // written coalesced in g-byte units, the strided side in the same units.
+// PackRun, udiv, pack_runs_units and the run folding: pack_runs.h (shared with pack_blocks.hip)
 // ---------------------------------------------------------------------------
-struct PackRun {
-    uint64_t pp;     // first packed unit of the run inside a packed element
-    uint64_t blk;    // units per block
-    uint64_t nrep;   // blocks in the run
-    int64_t off;     // unit offset of block 0 inside an element
-    int64_t stride;  // units between consecutive blocks
-};
+
 constexpr int kRunLds = 512;  // runs staged in LDS (20 KiB)
-
-__device__ __forceinline__ uint64_t udiv(uint64_t a, uint64_t b) {
-    return ((a | b) >> 32) ? a / b : (uint64_t)((uint32_t)a / (uint32_t)b);
-}
-
-template <typename G>
-__device__ __forceinline__ void pack_runs_units(const G *__restrict__ src, G *__restrict__ dst, uint64_t ext,
-                                                uint64_t upe, uint64_t total, uint64_t step, uint64_t u,
-                                                const PackRun *rt, int nrun, int unpack) {
-    // (element, unit-in-element) advanced incrementally: no per-unit 64-bit division
-    uint64_t e = udiv(u, upe), q = u - e * upe;
-    const uint64_t se = udiv(step, upe), sq = step - se * upe;
-    for (; u < total; u += step) {
-        int lo = 0, hi = nrun;  // largest k with pp[k] <= q
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (rt[mid].pp <= q) lo = mid;
-            else hi = mid;
-        }
-        const PackRun r = rt[lo];
-        const uint64_t w = q - r.pp;
-        const uint64_t i = r.nrep > 1 ? udiv(w, r.blk) : 0;
-        const int64_t su = (int64_t)(e * ext) + r.off + (int64_t)i * r.stride + (int64_t)(w - i * r.blk);
-        if (!unpack) dst[u] = src[su];
-        else dst[su] = src[u];
-        q += sq;
-        e += se;
-        if (q >= upe) {
-            q -= upe;
-            ++e;
-        }
-    }
-}
 
 template <typename G>
 __global__ __launch_bounds__(kThreads) void k_pack_runs(const G *__restrict__ src, G *__restrict__ dst,
@@ -191,48 +154,16 @@ int launch_pack_runs(const void *src, void *dst, size_t count, size_t extent, co
     while (g > 1 && (acc % (uint64_t)g)) g >>= 1;
     // equal-length blocks at a constant distance fold into one run
     std::vector<PackRun> runs;
-    uint64_t pp = 0;
-    for (int s = 0; s < nseg; ++s) {
-        const int64_t off = offs[s] / g, len = lens[s] / g;
-        if (!runs.empty()) {
-            PackRun &r = runs.back();
-            const int64_t last = r.off + (int64_t)(r.nrep - 1) * r.stride;
-            if ((int64_t)r.blk == len && (r.nrep == 1 || off - last == r.stride)) {
-                if (r.nrep == 1) r.stride = off - last;
-                ++r.nrep;
-                pp += (uint64_t)len;
-                continue;
-            }
-        }
-        runs.push_back(PackRun{pp, (uint64_t)len, 1, off, 0});
-        pp += (uint64_t)len;
-    }
+    const uint64_t upe = fold_runs(offs, lens, nseg, g, runs);
     const int nrun = (int)runs.size();
-    // device copy of the run table: pinned staging + device buffer, grown on demand
-    // (every C-ABI call ends stream-synchronised, so the previous table is no longer read)
-    static PackRun *h_tab = nullptr, *d_tab = nullptr;
-    static size_t cap = 0;
-    if ((size_t)nrun > cap) {
-        (void)hipStreamSynchronize(stream);
-        if (h_tab) (void)hipHostFree(h_tab);
-        if (d_tab) (void)hipFree(d_tab);
-        h_tab = d_tab = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(64, 2 * (size_t)nrun);
-        if (hipHostMalloc((void **)&h_tab, want * sizeof(PackRun), hipHostMallocDefault) != hipSuccess ||
-            hipMalloc((void **)&d_tab, want * sizeof(PackRun)) != hipSuccess)
-            return E_NO_MEM;
-        cap = want;
-    }
-    memcpy(h_tab, runs.data(), (size_t)nrun * sizeof(PackRun));
-    if (hipMemcpyAsync(d_tab, h_tab, (size_t)nrun * sizeof(PackRun), hipMemcpyHostToDevice, stream) != hipSuccess)
-        return E_INTERN;
-    const uint64_t upe = pp, ext_u = extent / (size_t)g, total = (uint64_t)count * upe;
+    static RunTable tab;
+    if (int rc = tab.upload(runs, stream)) return rc;
+    const uint64_t ext_u = extent / (size_t)g, total = (uint64_t)count * upe;
     size_t grid = (total + kThreads - 1) / kThreads;
     if (grid > 4096) grid = 4096;
 #define MV2_RUNS(G)                                                                                          \
     hipLaunchKernelGGL(k_pack_runs<G>, dim3(grid), dim3(kThreads), 0, stream, (const G *)src, (G *)dst,     \
-                       (uint64_t)count, ext_u, upe, d_tab, nrun, unpack, done)
+                       (uint64_t)count, ext_u, upe, tab.d_tab, nrun, unpack, done)
     switch (g) {
     case 16: MV2_RUNS(v4u); break;
     case 8: MV2_RUNS(uint64_t); break;

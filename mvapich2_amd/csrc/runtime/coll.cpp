@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../../include/mv2h.h"
+#include "../pack/pack_blocks.h"
 #include "coll_internal.h"
 #include "internode.h"
 #include "log.h"
@@ -74,6 +75,14 @@ static int pack_call(void *stream, Launch launch) {
     if (int rc = ensure_init_for_device()) return rc;
     hipStream_t st = pick_stream(stream);
     return launch_finish(st, [&] { return launch(st, arm_done(st)); });
+}
+
+// The run-table kernels' table (pack/pack_runs.h RunTable) is rewritten in its pinned staging per
+// launch.  A blocking call has waited for the previous launch; one initiated without a wait
+// (nonblocking, stream-ordered) may still have the previous table's copy queued, so it waits here.
+static int settle_run_table(hipStream_t st) {
+    const World &w = world();
+    return (w.defer || w.enqueue) && hipStreamSynchronize(st) != hipSuccess ? (int)E_INTERN : 0;
 }
 
 // Several nodes: the reference's SMP-aware shape (scan.c:267-406: a scan per node, a scan over the
@@ -179,6 +188,7 @@ int mv2h_set_tuning(const char *key, long value) {
     else if (!strcmp(key, "withhold_done")) withhold_done((int)value);
     else if (!strcmp(key, "fake_split")) fake_split((int)value);
     else if (!strcmp(key, "agv_via_a2a")) set_agv_via_a2a((int)value);
+    else if (!strcmp(key, "pack_blocks")) w.pack_blocks = value != 0;
     else if (!strcmp(key, "oneshot_max")) {
         if ((size_t)value > w.slot_bytes && w.size > 1) return E_ARG;
         w.oneshot_max = (size_t)value;
@@ -217,6 +227,9 @@ int mv2h_get_info(const char *key, long *value) {
     else if (!strcmp(key, "gv_oneshot_bytes")) *value = (long)gv_path_calls(1);
     else if (!strcmp(key, "gv_pipe")) *value = (long)gv_path_calls(2);
     else if (!strcmp(key, "gv_pipe_shift")) *value = (long)gv_path_calls(3);
+    else if (!strcmp(key, "pack_blocks")) *value = w.pack_blocks;
+    else if (!strcmp(key, "pack_blocks_calls")) *value = (long)w.pack_blocks_calls;
+    else if (!strcmp(key, "pack_blocks_global_tab")) *value = (long)w.pack_blocks_global_tab;
     else if (!strcmp(key, "call_allocs")) *value = (long)w.call_allocs;
     else if (!strcmp(key, "pool_trims")) *value = (long)w.pool_trims;
     else if (!strcmp(key, "rl_tiny_max")) *value = (long)w.rl_tiny_max;
@@ -687,8 +700,48 @@ int mv2h_unpack_strided(const void *src, void *dst, size_t nblocks, size_t blk, 
 int mv2h_pack_segments(const void *src, void *dst, size_t count, size_t extent, const int64_t *offs,
                        const int64_t *lens, int nseg, int unpack, void *stream) {
     return pack_call(stream, [&](hipStream_t st, Done d) {
+        if (int rc = settle_run_table(st)) return rc;
         return launch_pack_runs(src, dst, count, extent, offs, lens, nseg, unpack ? 1 : 0, st, d);
     });
+}
+
+// Up to kMaxRanks differently-typed blocks in one launch (pack/pack_blocks.hip).  The arguments are
+// checked and the launch prepared on the host first: an argument error or a call whose blocks are
+// all empty launches nothing (and arms no completion word).
+int mv2h_pack_blocks(void *base, void *packed, int nblk, const int64_t *disp, const size_t *count, const size_t *extent,
+                     const size_t *packed_off, const int *seg_first, const int64_t *offs, const int64_t *lens, int unpack,
+                     void *stream) {
+    World &w = world();
+    PackBlocksJob job;
+    if (int rc = pack_blocks_prepare(base, packed, nblk, disp, count, extent, packed_off, seg_first, offs, lens,
+                                     w.max_grid, &job))
+        return rc;
+    if (!job.grid) return 0;
+    if (!base || !packed) return E_ARG;
+    return pack_call(stream, [&](hipStream_t st, Done d) {
+        if (int rc = settle_run_table(st)) return rc;
+        const int rc = launch_pack_blocks(base, packed, job, unpack ? 1 : 0, st, d);
+        if (!rc) {
+            ++w.pack_blocks_calls;
+            w.pack_blocks_global_tab += job.global_tab;
+        }
+        return rc;
+    });
+}
+
+int mv2h_pack_blocks_plan(int n, const size_t *units, long max_grid, int *wg0, int *nwg, int *grid, size_t *tile) {
+    if (n < 1 || n > kMaxRanks || !units) return E_ARG;
+    uint64_t u[kMaxRanks];
+    uint32_t first[kMaxRanks], cnt[kMaxRanks];
+    for (int b = 0; b < n; ++b) u[b] = units[b];
+    const int g = pack_blocks_plan(n, u, max_grid > 0 ? max_grid : world().max_grid, first, cnt);
+    for (int b = 0; b < n; ++b) {
+        if (wg0) wg0[b] = (int)first[b];
+        if (nwg) nwg[b] = (int)cnt[b];
+    }
+    if (grid) *grid = g;
+    if (tile) *tile = (size_t)kPackBlocksTile;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

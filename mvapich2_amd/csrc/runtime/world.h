@@ -193,6 +193,11 @@ struct World {
     // device allocations made inside MPI calls (scratch growth: hipMalloc, each paired with a
     // hipFree that synchronises the device); stays flat once the scratch caches are warm
     uint64_t call_allocs = 0;
+    // the batched block pack (pack/pack_blocks.hip): 0 sends MPI_Alltoallw / a derived-type
+    // MPI_Alltoallv down the per-block MPI_Pack route instead (mv2h_set_tuning "pack_blocks");
+    // launches, and those of them in which some block's run slice did not fit in LDS
+    int pack_blocks = 1;
+    uint64_t pack_blocks_calls = 0, pack_blocks_global_tab = 0;
     uint64_t pool_trims = 0;  // idle pool blocks returned to HIP above MV2AMD_POOL_IDLE_MAX (world.cpp pool_put)
     // completion-word events (call.cpp wait_done), reported by mv2h_get_info and both bench lines:
     // the stream was consulted (the word unseen 200 us after the launch); the word was seen only
