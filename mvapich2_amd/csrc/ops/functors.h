@@ -99,9 +99,12 @@ template <typename F> __device__ __forceinline__ F fadd(F a, F b) { return x86_n
 template <typename F> __device__ __forceinline__ F fsub(F a, F b) { return x86_nan<F>(a - b, a, b); }
 template <typename F> __device__ __forceinline__ F fmul(F a, F b) { return x86_nan<F>(a * b, a, b); }
 
-// C99 Annex G complex multiply (the libgcc __mulsc3 / __muldc3 algorithm)
+// C99 Annex G complex multiply (the libgcc __mulsc3 / __muldc3 algorithm).  Which operand is the
+// first of an SSE instruction decides whose NaN survives when both are NaN (x86_nan): libgcc's
+// compiled b * c has c first, the other three products run in source order (oracle:
+// tests/test_gpu_reduce_local.py test_complex_prod_nan_operand_order).
 template <typename F> __device__ __forceinline__ void annexg_mul(F a, F b, F c, F d, F &x, F &y) {
-    F ac = fmul(a, c), bd = fmul(b, d), ad = fmul(a, d), bc = fmul(b, c);
+    F ac = fmul(a, c), bd = fmul(b, d), ad = fmul(a, d), bc = fmul(c, b);
     x = fsub(ac, bd);
     y = fadd(ad, bc);
     if (__builtin_isnan(x) && __builtin_isnan(y)) {
@@ -193,8 +196,10 @@ struct R<OP, K, typename std::enable_if<(K >= K_CF32_C99 && K <= K_CF64_S)>::typ
         } else if constexpr (OP == OP_PROD) {
             if constexpr (K == K_CF32_S || K == K_CF64_S) {
                 // opprod.c:50-51: c = a; re = c.re*b.re - c.im*b.im; im = c.im*b.re + c.re*b.im
-                r.re = fsub(fmul(a.re, b.re), fmul(a.im, b.im));
-                r.im = fadd(fmul(a.im, b.re), fmul(a.re, b.im));
+                // gcc -O2 multiplies with b's part as the first (destination) operand in all but
+                // c.im*b.re, so b's NaN survives there when both factors are NaN (x86_nan)
+                r.re = fsub(fmul(b.re, a.re), fmul(b.im, a.im));
+                r.im = fadd(fmul(a.im, b.re), fmul(b.im, a.re));
             } else {
                 annexg_mul(a.re, a.im, b.re, b.im, r.re, r.im);
             }

@@ -671,6 +671,41 @@ def staged(L, case, rank, n):
     return rb.get(out_bytes if coll != "reduce" or rank == root else 0)
 
 
+def batch(L, case, rank, n):
+    """Many blocking MPI_Allreduce / MPI_Reduce / MPI_Reduce_scatter calls (case["cases"], each with the
+    fields of a case of that kind) on one send and one receive buffer allocated once; the receive
+    buffer is refilled with 0xA5 before every call.  Returns every call's result bytes concatenated
+    (a reduce: the root's only), so a matrix of a thousand calls leaves one file per rank."""
+    subs = case["cases"]
+    cap = max(sub["count"] * TYPES[sub["type"]][3] for sub in subs)
+    sb, rb = m.DeviceBuffer(cap), m.DeviceBuffer(cap)
+    fill = np.full(cap, 0xA5, dtype=np.uint8)
+    parts = []
+    for sub in subs:
+        k, h, ext, op = sub["kind"], TYPES[sub["type"]][0], TYPES[sub["type"]][3], OPS[sub["op"]]
+        count = sub["count"]
+        sb.upload(inputs(sub, rank))
+        if k == "reduce_scatter":
+            counts = sub["recvcounts"]
+            assert sum(counts) == count
+            got = counts[rank] * ext
+            rb.upload(fill[:got])
+            rc = L.MPI_Reduce_scatter(sb.ptr, rb.ptr, (ctypes.c_int * n)(*counts), h, op, WORLD)
+        else:
+            got = count * ext
+            rb.upload(fill[:got])
+            if k == "allreduce":
+                rc = L.MPI_Allreduce(sb.ptr, rb.ptr, count, h, op, WORLD)
+            elif k == "reduce":
+                rc = L.MPI_Reduce(sb.ptr, rb.ptr, count, h, op, sub["root"], WORLD)
+                got = got if rank == sub["root"] else 0
+            else:
+                raise ValueError(k)
+        assert rc == 0, (sub["id"], rc)
+        parts.append(rb.download(np.uint8, count=got))
+    return np.concatenate(parts)
+
+
 def main():
     spec = json.load(open(sys.argv[1]))
     out = sys.argv[2]
@@ -726,6 +761,8 @@ def main():
                 rc = L.MPI_Reduce(sb.ptr, rb.ptr, count, h, op, case["root"], WORLD)
             assert rc == 0, (case["id"], rc)
             res = rb.download(np.uint8, count=count * ext)
+        elif k == "batch":  # many reducing calls on buffers allocated once, one result file
+            res = batch(L, case, rank, n)
         elif k == "graph_allreduce":  # HIP graph capture of MPIX_Allreduce_enqueue (graph lane)
             res = graph_allreduce(L, case, rank, n)
         elif k == "graph_collectives":  # every stream-ordered collective in one captured graph
@@ -757,6 +794,7 @@ def main():
             for call in case["calls"]:
                 cnt, tt = call["count"], TYPES[call["type"]][0]
                 e = TYPES[call["type"]][3]
+                rcounts = call.get("recvcounts", [cnt] * n)  # a reduce_scatter's blocks (default: cnt each)
                 sb, rb = m.DeviceBuffer(max(16, cnt * e * n)), m.DeviceBuffer(max(16, cnt * e * n))
                 if call["coll"] == "allreduce":
                     src = ctypes.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF) if call.get("in_place") else sb.ptr
@@ -764,8 +802,7 @@ def main():
                 elif call["coll"] == "reduce":
                     rc = L.MPI_Reduce(sb.ptr, rb.ptr, cnt, tt, OPS["MPI_SUM"], call["root"], WORLD)
                 else:
-                    rc = L.MPI_Reduce_scatter(sb.ptr, rb.ptr, (ctypes.c_int * n)(*([cnt] * n)), tt, OPS["MPI_SUM"],
-                                              WORLD)
+                    rc = L.MPI_Reduce_scatter(sb.ptr, rb.ptr, (ctypes.c_int * n)(*rcounts), tt, OPS["MPI_SUM"], WORLD)
                 assert rc == 0, (call, rc)
             assert L.MPI_T_pvar_stop(sess, ctypes.c_void_p.in_dll(L, "MPI_T_PVAR_ALL_HANDLES")) == 0
             vals = {}

@@ -24,7 +24,7 @@ FILL = 0xA5
 
 def inputs(case, rank, call=0):
     rng = np.random.default_rng(case["seed"] * 1000 + call * 100 + rank)
-    return rand_typed(case["type"], case["count"], rng, ties=case.get("ties", False))
+    return rand_typed(case["type"], case["count"], rng, small=case.get("small", False), ties=case.get("ties", False))
 
 
 def scan_call(L, case, x, h, op, count, ext):
@@ -48,6 +48,25 @@ def scan_call(L, case, x, h, op, count, ext):
     return rb.download(np.uint8, count=count * ext)
 
 
+def scan_batch(L, case, rank):
+    """Many blocking MPI_Scan / MPI_Exscan calls (case["cases"], each with the fields of a "scan" case)
+    on one send and one receive buffer allocated once; the receive buffer is refilled with 0xA5 before
+    every call.  Returns every call's receive buffer concatenated: one file per rank."""
+    subs = case["cases"]
+    cap = max(sub["count"] * TYPES[sub["type"]][3] for sub in subs)
+    sb, rb = m.DeviceBuffer(cap), m.DeviceBuffer(cap)
+    fill = np.full(cap, FILL, dtype=np.uint8)
+    parts = []
+    for sub in subs:
+        h, ext, count = TYPES[sub["type"]][0], TYPES[sub["type"]][3], sub["count"]
+        sb.upload(inputs(sub, rank))
+        rb.upload(fill[:count * ext])
+        rc = (L.MPI_Exscan if sub["coll"] == "exscan" else L.MPI_Scan)(sb.ptr, rb.ptr, count, h, OPS[sub["op"]], WORLD)
+        assert rc == 0, (sub["id"], rc)
+        parts.append(rb.download(np.uint8, count=count * ext))
+    return np.concatenate(parts)
+
+
 def main():
     spec = json.load(open(sys.argv[1]))
     out = sys.argv[2]
@@ -63,6 +82,8 @@ def main():
         count = case.get("count", 0)
         if k == "scan":
             res = scan_call(L, case, inputs(case, rank), h, OPS[case["op"]], count, ext)
+        elif k == "scan_batch":
+            res = scan_batch(L, case, rank)
         elif k == "user_scan":  # inout = 2 in + 3 inout on int32, commutative flag as the case says
             FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
                                   ctypes.POINTER(ctypes.c_int))

@@ -38,6 +38,40 @@ def test_all_pairs_bit_exact(count):
             assert_bytes_equal(got, want, t, count, f"{op} off={off}")
 
 
+def nan_operand_grid(tname):
+    """(in, inout) complex operands whose four parts run through every combination of a positive
+    and a negative NaN with different payloads, both infinities, 0, two finite values and a value
+    whose products overflow: whenever both factors of a product are NaN, the result tells which
+    operand the reference's compiled multiply takes first"""
+    cdt = m.np_dtype(tname)
+    f = np.dtype(f"f{cdt.itemsize // 2}")
+    u = np.dtype(f"u{f.itemsize}")
+    nans = [0x7FC00011, 0xFFC00022] if f.itemsize == 4 else [0x7FF8000000000011, 0xFFF8000000000022]
+    vals = np.concatenate([np.array(nans, dtype=u).view(f),
+                           np.array([np.inf, -np.inf, 0.0, 1.5, -2.0, np.finfo(f).max / 2], dtype=f)])
+    a, b, c, d = (g.ravel() for g in np.meshgrid(vals, vals, vals, vals, indexing="ij"))
+    x, y = np.empty(a.size, dtype=cdt), np.empty(a.size, dtype=cdt)
+    y.real, y.imag, x.real, x.imag = a, b, c, d
+    return x, y
+
+
+@pytest.mark.parametrize("t", ["MPI_COMPLEX", "MPI_DOUBLE_COMPLEX", "MPI_C_FLOAT_COMPLEX", "MPI_C_DOUBLE_COMPLEX"])
+def test_complex_prod_nan_operand_order(t):
+    """A chain of three complex products meets NaNs of different signs (the default NaN x86 makes
+    is negative, an input NaN positive), so the NaN a product of two NaNs keeps must be the one
+    the reference's compiled code keeps: the struct kinds' loop (opprod.c) and libgcc's Annex G
+    multiply each run some of their products with the second factor first.  (MPI_SUM is left out on
+    purpose: the oracle's C99 loop adds the imaginary parts with `in` first while the same loop
+    compiled on its own adds them `inout` first -- register allocation in one build, nothing the
+    reference defines -- and the struct and C99 kinds share one SUM kernel.)"""
+    x, y = nan_operand_grid(t)
+    count = len(x)
+    assert count == 8 ** 4
+    want = y.copy()
+    assert oracle.reduce_local(x, want, count, TYPES[t][0], OPS["MPI_PROD"]) == 0
+    assert_bytes_equal(run_rl(t, "MPI_PROD", x, y, count), want, t, count, "MPI_PROD")
+
+
 def test_reduce_local_c_known_answers(golden):
     cases, arrs = golden
     for c in cases:

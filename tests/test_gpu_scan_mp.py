@@ -33,12 +33,13 @@ MPI_ERR_OTHER = 15
 
 def inputs(case, rank, call=0):
     rng = np.random.default_rng(case["seed"] * 1000 + call * 100 + rank)
-    return rand_typed(case["type"], case["count"], rng, ties=case.get("ties", False))
+    return rand_typed(case["type"], case["count"], rng, small=case.get("small", False), ties=case.get("ties", False))
 
 
-def run_scan_workers(n, cases, tmp_path, timeout=100, ppn=None):
+def run_scan_workers(n, cases, tmp_path, timeout=100, ppn=None, extra_env=None):
     """n ranks of tests/mp_scan_worker.py, launched as test_gpu_collectives_mp.run_workers launches its
-    worker; ppn < n emulates n / ppn nodes (node-major ranks, leaders linked over 127.0.0.1)"""
+    worker; ppn < n emulates n / ppn nodes (node-major ranks, leaders linked over 127.0.0.1);
+    extra_env: settings on top of the "small" geometry"""
     spec = tmp_path / "spec.json"
     spec.write_text(json.dumps({"cases": cases}))
     out = tmp_path / "out"
@@ -58,7 +59,7 @@ def run_scan_workers(n, cases, tmp_path, timeout=100, ppn=None):
     for r in range(n):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(n), LOCAL_RANK=str(r % ppn), LOCAL_WORLD_SIZE=str(ppn),
                    MV2AMD_JOBID=jobid)
-        env.update({"MV2AMD_TIMEOUT_S": "30", **boot, **GEOMS["small"]})
+        env.update({"MV2AMD_TIMEOUT_S": "30", **boot, **GEOMS["small"], **(extra_env or {})})
         env.pop("MV2AMD_DEVICE", None)
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "mp_scan_worker.py"), str(spec),
                                        str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
