@@ -4,18 +4,9 @@
 
 namespace mv2 {
 
-// One all-to-all over this node's ranks (MPI_Alltoall: every pair the same length; MPI_Alltoallv:
-// a length per pair).  Rank me sends slen[j] bytes at send + soff[j] to rank j and receives
-// rlen[j] bytes from rank j at recv + roff[j]; slen[j] on rank me equals rlen[me] on rank j.
-// send and recv are 16-byte aligned (the runtime stages anything else); the offsets are not.
-struct A2AArgs {
-    int n, me;
-    const char *send;
-    char *recv;
-    size_t soff[kMaxRanks], slen[kMaxRanks];
-    size_t roff[kMaxRanks], rlen[kMaxRanks];
-    // smis[j]: rank j's (soff[me] & 15), the misalignment its block arrives with (pipelined kernel)
-    uint32_t smis[kMaxRanks];
+// The per-call part of a table launch, the last member of both argument structs below: what the
+// runtime reserves for the call (runtime/coll_table.cpp table_reserve) and nothing of the table.
+struct TableRt {
     // one-shot kernel: nvec = 16-byte vectors of the longest pair, partitioned over the workgroups
     // (every offset and length is then a multiple of 16); 0 = byte by byte through workgroup 0
     PeerTableW arena_peer;  // peers' one-shot arena (this call's half); my slot at + me * slot_bytes
@@ -37,6 +28,21 @@ struct A2AArgs {
     DevSeq *dseq;  // graph lane
 };
 
+// One all-to-all over this node's ranks (MPI_Alltoall: every pair the same length; MPI_Alltoallv:
+// a length per pair).  Rank me sends slen[j] bytes at send + soff[j] to rank j and receives
+// rlen[j] bytes from rank j at recv + roff[j]; slen[j] on rank me equals rlen[me] on rank j.
+// send and recv are 16-byte aligned (the runtime stages anything else); the offsets are not.
+struct A2AArgs {
+    int n, me;
+    const char *send;
+    char *recv;
+    size_t soff[kMaxRanks], slen[kMaxRanks];
+    size_t roff[kMaxRanks], rlen[kMaxRanks];
+    // smis[j]: rank j's (soff[me] & 15), the misalignment its block arrives with (pipelined kernel)
+    uint32_t smis[kMaxRanks];
+    TableRt rt;
+};
+
 // One gather over this node's ranks (MPI_Allgatherv: every rank receives; MPI_Gather: the root
 // alone).  Rank me has one block, slen bytes at send, for the ranks of dmask; the own bit means
 // "also copy it to my own recv + roff[me], unless it is already there".  It gathers rlen[j] bytes
@@ -51,24 +57,14 @@ struct GvArgs {
     unsigned dmask;
     char *recv;
     size_t roff[kMaxRanks], rlen[kMaxRanks];
-    // the rest as in A2AArgs
-    PeerTableW arena_peer;
-    const char *arena_own;
-    size_t nvec, slot_bytes, half;
-    PeerTableW ag_peer;
-    size_t tseg, tsub;
-    uint64_t round0;
-    int nrounds;
-    int rnt;
-    SigTable sig_peer;
-    uint64_t *sig_own;
-    uint64_t epoch0;
-    int light;
-    int *err;
-    uint64_t timeout;
-    Done done;
-    DevSeq *dseq;
+    TableRt rt;
 };
+
+// the kernarg layout the kernels were measured with, from before the block was one struct
+static_assert(sizeof(A2AArgs) == 640 && offsetof(A2AArgs, rt.arena_peer) == 312 && offsetof(A2AArgs, rt.dseq) == 632,
+              "A2AArgs layout");
+static_assert(sizeof(GvArgs) == 496 && offsetof(GvArgs, rt.arena_peer) == 168 && offsetof(GvArgs, rt.dseq) == 488,
+              "GvArgs layout");
 
 int launch_oneshot_a2a(const A2AArgs &a, const LaunchCfg &cfg);
 int launch_pipe_a2a(const A2AArgs &a, const LaunchCfg &cfg);

@@ -20,6 +20,55 @@
 namespace mv2 {
 
 // ---------------------------------------------------------------------------
+// What the four kernels share, all of it read from the per-call part of their arguments (TableRt).
+// ---------------------------------------------------------------------------
+
+// The call's flag epoch (pipelined: its first), first round and one-shot arena half; on the graph
+// lane this replay's, read from the device before any workgroup can advance them.
+struct TableCall {
+    uint64_t epoch, round0;
+    size_t poff;
+};
+__device__ __forceinline__ TableCall table_call(const TableRt &rt) {
+    TableCall c{rt.epoch0, rt.round0, 0};
+    if (rt.dseq) {
+        const SeqBase q = dseq_read(rt.dseq);
+        c = TableCall{q.epoch + 1, q.round, (q.os & 1) * rt.half};
+    }
+    return c;
+}
+
+// The end of a kernel: the graph lane's sequence block advanced, the completion word raised.
+__device__ __forceinline__ void table_end(const TableRt &rt, uint64_t epochs, uint64_t rounds, uint64_t os) {
+    if (rt.dseq) dseq_advance(rt.dseq, epochs, rounds, os);
+    block_done(rt.done);
+}
+
+// One-shot, after the wait: slot [j] of my arena to recv + roff[j], as vectors [vb, ve) or, from
+// workgroup 0, byte by byte.
+template <class Args>
+__device__ __forceinline__ void slot_to_recv(const Args &a, int j, int blk, size_t poff, size_t vb, size_t ve) {
+    const char *slot = a.rt.arena_own + poff + (size_t)j * a.rt.slot_bytes;
+    char *dst = a.recv + a.roff[j];
+    const size_t len = a.rlen[j];
+    if (a.rt.nvec) {
+        const size_t nv = len >> 4, e = ve < nv ? ve : nv;
+        for (size_t i = vb + threadIdx.x; i < e; i += kThreads) ((v4u *)dst)[i] = ld_nt((const v4u *)slot + i);
+    } else if (blk == 0) {
+        for (size_t i = threadIdx.x; i < len; i += kThreads) dst[i] = __builtin_nontemporal_load(slot + i);
+    }
+}
+
+// Pipelined, round k: the slot parity, the flag epoch and where workgroup b's range starts.
+struct PipeRound {
+    uint64_t par, E;
+    size_t rbase;
+};
+__device__ __forceinline__ PipeRound pipe_round(const TableRt &rt, const TableCall &c, int k, size_t so) {
+    return PipeRound{(c.round0 + (uint64_t)k) & 1, c.epoch + 2 * (uint64_t)k, (size_t)k * rt.tseg + so};
+}
+
+// ---------------------------------------------------------------------------
 // One-shot kernel.  Rank me pushes block j of its send buffer into slot [me] of rank j's one-shot
 // arena (this call's half) and copies its own block locally, raises its flag to every peer, waits
 // for every peer's flag, and copies slot [j] to recv + roff[j] for every j != me.  Every rank
@@ -32,48 +81,31 @@ namespace mv2 {
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_oneshot_a2a(A2AArgs a) {
     const int blk = blockIdx.x, G = gridDim.x;
-    const size_t per = (a.nvec + G - 1) / G;
+    const size_t per = (a.rt.nvec + G - 1) / G;
     const size_t vb = (size_t)blk * per, ve = vb + per;
-    uint64_t epoch = a.epoch0;
-    size_t poff = 0;
-    if (a.dseq) {  // graph lane: this replay's epoch and arena half
-        const SeqBase q = dseq_read(a.dseq);
-        epoch = q.epoch + 1;
-        poff = (q.os & 1) * a.half;
-    }
-    const size_t myslot = poff + (size_t)a.me * a.slot_bytes;
+    const TableCall c = table_call(a.rt);
+    const size_t myslot = c.poff + (size_t)a.me * a.rt.slot_bytes;
 #pragma unroll
     for (int j = 0; j < kMaxRanks; ++j) {
         if (j >= a.n) continue;
         const char *src = a.send + a.soff[j];
-        char *dst = j == a.me ? a.recv + a.roff[j] : a.arena_peer.p[j] + myslot;
+        char *dst = j == a.me ? a.recv + a.roff[j] : a.rt.arena_peer.p[j] + myslot;
         if (src == dst) continue;  // in place: my own block stays where it is
         const size_t len = a.slen[j];
-        if (a.nvec) {
+        if (a.rt.nvec) {
             const size_t nv = len >> 4, e = ve < nv ? ve : nv;
             for (size_t i = vb + threadIdx.x; i < e; i += kThreads) ((v4u *)dst)[i] = ((const v4u *)src)[i];
         } else if (blk == 0) {
             for (size_t i = threadIdx.x; i < len; i += kThreads) dst[i] = src[i];
         }
     }
-    signal_peers(a.sig_peer, a.n, a.me, blk, epoch, a.light != 0);
-    if (wait_peers(a.sig_own, a.n, blk, epoch, a.err, a.timeout, a.light != 0)) {
+    signal_peers(a.rt.sig_peer, a.n, a.me, blk, c.epoch, a.rt.light != 0);
+    if (wait_peers(a.rt.sig_own, a.n, blk, c.epoch, a.rt.err, a.rt.timeout, a.rt.light != 0)) {
 #pragma unroll
-        for (int j = 0; j < kMaxRanks; ++j) {
-            if (j >= a.n || j == a.me) continue;
-            const char *slot = a.arena_own + poff + (size_t)j * a.slot_bytes;
-            char *dst = a.recv + a.roff[j];
-            const size_t len = a.rlen[j];
-            if (a.nvec) {
-                const size_t nv = len >> 4, e = ve < nv ? ve : nv;
-                for (size_t i = vb + threadIdx.x; i < e; i += kThreads) ((v4u *)dst)[i] = ld_nt((const v4u *)slot + i);
-            } else if (blk == 0) {
-                for (size_t i = threadIdx.x; i < len; i += kThreads) dst[i] = __builtin_nontemporal_load(slot + i);
-            }
-        }
+        for (int j = 0; j < kMaxRanks; ++j)
+            if (j < a.n && j != a.me) slot_to_recv(a, j, blk, c.poff, vb, ve);
     }
-    if (a.dseq) dseq_advance(a.dseq, 1, 0, 1);
-    block_done(a.done);
+    table_end(a.rt, 1, 0, 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -205,66 +237,46 @@ __device__ __forceinline__ size_t a2a_range(size_t len, size_t rbase, size_t tsu
 }
 
 __global__ __launch_bounds__(kPipeThreads) void k_pipe_a2a(A2AArgs a) {
-    uint64_t epoch0 = a.epoch0, round0 = a.round0;
-    if (a.dseq) {  // graph lane: this replay's base, read before any workgroup can advance it
-        const SeqBase q = dseq_read(a.dseq);
-        epoch0 = q.epoch + 1;
-        round0 = q.round;
-    }
+    const TableCall c = table_call(a.rt);
     const int b = blockIdx.x, n = a.n, me = a.me;
     const unsigned all = (1u << n) - 1u;
-    const size_t so = (size_t)b * a.tsub;
-    for (int k = 0; k < a.nrounds; ++k) {
-        const uint64_t par = (round0 + (uint64_t)k) & 1;
-        const uint64_t E = epoch0 + 2 * (uint64_t)k;
-        const size_t rbase = (size_t)k * a.tseg + so;
+    const size_t so = (size_t)b * a.rt.tsub;
+    for (int k = 0; k < a.rt.nrounds; ++k) {
+        const PipeRound r = pipe_round(a.rt, c, k, so);
         {
             Jobs jb{}, own{};
 #pragma unroll
             for (int j = 0; j < kMaxRanks; ++j) {
                 if (j >= n) continue;
-                const char *src = a.send + a.soff[j] + rbase;
-                const size_t len = a2a_range(a.slen[j], rbase, a.tsub);
+                const char *src = a.send + a.soff[j] + r.rbase;
+                const size_t len = a2a_range(a.slen[j], r.rbase, a.rt.tsub);
                 if (j != me) {
                     jb.src[j] = src;
-                    jb.dst[j] = pslot(a.ag_peer.p[j], par, me) + so + (a.soff[j] & 15);
+                    jb.dst[j] = pslot(a.rt.ag_peer.p[j], r.par, me) + so + (a.soff[j] & 15);
                     jb.len[j] = len;
-                } else if (src != a.recv + a.roff[j] + rbase) {
+                } else if (src != a.recv + a.roff[j] + r.rbase) {
                     own.src[j] = src;
-                    own.dst[j] = a.recv + a.roff[j] + rbase;
+                    own.dst[j] = a.recv + a.roff[j] + r.rbase;
                     own.len[j] = len;
                 }
             }
-            blk_copy_jobs<false>(jb, a.rnt != 0);
+            blk_copy_jobs<false>(jb, a.rt.rnt != 0);
             blk_copy_local(own);
         }
-        signal_peers(a.sig_peer, n, me, b, E, a.light != 0);
-        if (!wait_mask(a.sig_own, all, b, E, a.err, a.timeout, a.light != 0)) break;
+        signal_peers(a.rt.sig_peer, n, me, b, r.E, a.rt.light != 0);
+        if (!wait_mask(a.rt.sig_own, all, b, r.E, a.rt.err, a.rt.timeout, a.rt.light != 0)) break;
         Jobs g{};
 #pragma unroll
         for (int j = 0; j < kMaxRanks; ++j) {
             if (j < n && j != me) {
-                g.src[j] = pslot(a.ag_peer.p[me], par, j) + so + a.smis[j];
-                g.dst[j] = a.recv + a.roff[j] + rbase;
-                g.len[j] = a2a_range(a.rlen[j], rbase, a.tsub);
+                g.src[j] = pslot(a.rt.ag_peer.p[me], r.par, j) + so + a.smis[j];
+                g.dst[j] = a.recv + a.roff[j] + r.rbase;
+                g.len[j] = a2a_range(a.rlen[j], r.rbase, a.rt.tsub);
             }
         }
         blk_copy_local(g);
     }
-    if (a.dseq) dseq_advance(a.dseq, 2 * (uint64_t)a.nrounds, (uint64_t)a.nrounds, 0);
-    block_done(a.done);
-}
-
-int launch_oneshot_a2a(const A2AArgs &a, const LaunchCfg &cfg) {
-    static const int cap = resident_grid((const void *)k_oneshot_a2a, cfg);
-    const int g = cfg.grid < cap ? cfg.grid : cap;
-    hipLaunchKernelGGL(k_oneshot_a2a, dim3(g), dim3(kThreads), 0, cfg.stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
-}
-
-int launch_pipe_a2a(const A2AArgs &a, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_pipe_a2a, dim3(cfg.grid), dim3(kPipeThreads), 0, cfg.stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+    table_end(a.rt, 2 * (uint64_t)a.rt.nrounds, (uint64_t)a.rt.nrounds, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -287,58 +299,41 @@ int launch_pipe_a2a(const A2AArgs &a, const LaunchCfg &cfg) {
 // workgroup 0 moves every block byte by byte (any address).
 __global__ __launch_bounds__(kThreads) void k_oneshot_gv(GvArgs a) {
     const int blk = blockIdx.x, G = gridDim.x;
-    const size_t per = (a.nvec + G - 1) / G;
+    const size_t per = (a.rt.nvec + G - 1) / G;
     const size_t vb = (size_t)blk * per, ve = vb + per;
-    uint64_t epoch = a.epoch0;
-    size_t poff = 0;
-    if (a.dseq) {  // graph lane: this replay's epoch and arena half
-        const SeqBase q = dseq_read(a.dseq);
-        epoch = q.epoch + 1;
-        poff = (q.os & 1) * a.half;
-    }
-    const size_t myslot = poff + (size_t)a.me * a.slot_bytes;
+    const TableCall c = table_call(a.rt);
+    const size_t myslot = c.poff + (size_t)a.me * a.rt.slot_bytes;
     // the own bit: also to my own recv + roff[me], unless the block is already there
     char *own = a.recv + a.roff[a.me];
     if (!((a.dmask >> a.me) & 1u) || own == a.send) own = nullptr;
     const unsigned peers = a.dmask & ~(1u << a.me);
     if (peers || own) {
-        if (a.nvec) {
+        if (a.rt.nvec) {
             const size_t nv = a.slen >> 4, e = ve < nv ? ve : nv;
             for (size_t i = vb + threadIdx.x; i < e; i += kThreads) {
                 const v4u v = ((const v4u *)a.send)[i];
 #pragma unroll
                 for (int j = 0; j < kMaxRanks; ++j)
-                    if (j < a.n && ((peers >> j) & 1u)) ((v4u *)(a.arena_peer.p[j] + myslot))[i] = v;
+                    if (j < a.n && ((peers >> j) & 1u)) ((v4u *)(a.rt.arena_peer.p[j] + myslot))[i] = v;
                 if (own) ((v4u *)own)[i] = v;
             }
         } else if (blk == 0) {
             for (size_t i = threadIdx.x; i < a.slen; i += kThreads) {
-                const char c = a.send[i];
+                const char ch = a.send[i];
 #pragma unroll
                 for (int j = 0; j < kMaxRanks; ++j)
-                    if (j < a.n && ((peers >> j) & 1u)) (a.arena_peer.p[j] + myslot)[i] = c;
-                if (own) own[i] = c;
+                    if (j < a.n && ((peers >> j) & 1u)) (a.rt.arena_peer.p[j] + myslot)[i] = ch;
+                if (own) own[i] = ch;
             }
         }
     }
-    signal_peers(a.sig_peer, a.n, a.me, blk, epoch, a.light != 0);
-    if (wait_peers(a.sig_own, a.n, blk, epoch, a.err, a.timeout, a.light != 0)) {
+    signal_peers(a.rt.sig_peer, a.n, a.me, blk, c.epoch, a.rt.light != 0);
+    if (wait_peers(a.rt.sig_own, a.n, blk, c.epoch, a.rt.err, a.rt.timeout, a.rt.light != 0)) {
 #pragma unroll
-        for (int j = 0; j < kMaxRanks; ++j) {
-            if (j >= a.n || j == a.me) continue;
-            const char *slot = a.arena_own + poff + (size_t)j * a.slot_bytes;
-            char *dst = a.recv + a.roff[j];
-            const size_t len = a.rlen[j];
-            if (a.nvec) {
-                const size_t nv = len >> 4, e = ve < nv ? ve : nv;
-                for (size_t i = vb + threadIdx.x; i < e; i += kThreads) ((v4u *)dst)[i] = ld_nt((const v4u *)slot + i);
-            } else if (blk == 0) {
-                for (size_t i = threadIdx.x; i < len; i += kThreads) dst[i] = __builtin_nontemporal_load(slot + i);
-            }
-        }
+        for (int j = 0; j < kMaxRanks; ++j)
+            if (j < a.n && j != a.me) slot_to_recv(a, j, blk, c.poff, vb, ve);
     }
-    if (a.dseq) dseq_advance(a.dseq, 1, 0, 1);
-    block_done(a.done);
+    table_end(a.rt, 1, 0, 1);
 }
 
 // Pipelined: k_pipe_a2a's tiling, parities and flags.  Round k:
@@ -349,66 +344,68 @@ __global__ __launch_bounds__(kThreads) void k_oneshot_gv(GvArgs a) {
 //   gather : slot [par][j] + b * tsub -> recv + roff[j] + range, shifted where that is off a
 //            16-byte boundary
 __global__ __launch_bounds__(kPipeThreads) void k_pipe_gv(GvArgs a) {
-    uint64_t epoch0 = a.epoch0, round0 = a.round0;
-    if (a.dseq) {  // graph lane: this replay's base, read before any workgroup can advance it
-        const SeqBase q = dseq_read(a.dseq);
-        epoch0 = q.epoch + 1;
-        round0 = q.round;
-    }
+    const TableCall c = table_call(a.rt);
     const int b = blockIdx.x, n = a.n, me = a.me;
     const unsigned all = (1u << n) - 1u;
     const unsigned peers = a.dmask & ~(1u << me);
-    const size_t so = (size_t)b * a.tsub;
+    const size_t so = (size_t)b * a.rt.tsub;
     char *own = a.recv + a.roff[me];
     if (!((a.dmask >> me) & 1u) || own == a.send) own = nullptr;
-    for (int k = 0; k < a.nrounds; ++k) {
-        const uint64_t par = (round0 + (uint64_t)k) & 1;
-        const uint64_t E = epoch0 + 2 * (uint64_t)k;
-        const size_t rbase = (size_t)k * a.tseg + so;
-        const size_t len = a2a_range(a.slen, rbase, a.tsub);
+    for (int k = 0; k < a.rt.nrounds; ++k) {
+        const PipeRound r = pipe_round(a.rt, c, k, so);
+        const size_t len = a2a_range(a.slen, r.rbase, a.rt.tsub);
         if (len && (peers || own)) {
             const bool own_eq = own && ((uintptr_t)own & 15) == 0;
             Dsts d{};
 #pragma unroll
             for (int j = 0; j < kMaxRanks; ++j)
-                if (j < n && ((peers >> j) & 1u)) d.p[j] = pslot(a.ag_peer.p[j], par, me) + so;
-            if (own_eq) d.p[kMaxRanks] = own + rbase;
-            if (peers || own_eq) blk_copy_multi(d, a.send + rbase, len, a.rnt != 0);
+                if (j < n && ((peers >> j) & 1u)) d.p[j] = pslot(a.rt.ag_peer.p[j], r.par, me) + so;
+            if (own_eq) d.p[kMaxRanks] = own + r.rbase;
+            if (peers || own_eq) blk_copy_multi(d, a.send + r.rbase, len, a.rt.rnt != 0);
             if (own && !own_eq) {
                 Jobs o{};
-                o.src[0] = a.send + rbase;
-                o.dst[0] = own + rbase;
+                o.src[0] = a.send + r.rbase;
+                o.dst[0] = own + r.rbase;
                 o.len[0] = len;
                 blk_copy_shift(o);
             }
         }
-        signal_peers(a.sig_peer, n, me, b, E, a.light != 0);
-        if (!wait_mask(a.sig_own, all, b, E, a.err, a.timeout, a.light != 0)) break;
+        signal_peers(a.rt.sig_peer, n, me, b, r.E, a.rt.light != 0);
+        if (!wait_mask(a.rt.sig_own, all, b, r.E, a.rt.err, a.rt.timeout, a.rt.light != 0)) break;
         Jobs g{};
 #pragma unroll
         for (int j = 0; j < kMaxRanks; ++j) {
             if (j < n && j != me) {
-                g.src[j] = pslot(a.ag_peer.p[me], par, j) + so;
-                g.dst[j] = a.recv + a.roff[j] + rbase;
-                g.len[j] = a2a_range(a.rlen[j], rbase, a.tsub);
+                g.src[j] = pslot(a.rt.ag_peer.p[me], r.par, j) + so;
+                g.dst[j] = a.recv + a.roff[j] + r.rbase;
+                g.len[j] = a2a_range(a.rlen[j], r.rbase, a.rt.tsub);
             }
         }
         blk_copy_local(g);
     }
-    if (a.dseq) dseq_advance(a.dseq, 2 * (uint64_t)a.nrounds, (uint64_t)a.nrounds, 0);
-    block_done(a.done);
+    table_end(a.rt, 2 * (uint64_t)a.rt.nrounds, (uint64_t)a.rt.nrounds, 0);
 }
 
+// Launchers.  A one-shot kernel runs on at most its resident grid: the flags pair workgroup b of
+// every rank, so every workgroup of the grid has to be running.
+template <class Args>
+static int launch_table(void (*k)(Args), const Args &a, int grid, int threads, hipStream_t st) {
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), 0, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+}
+int launch_oneshot_a2a(const A2AArgs &a, const LaunchCfg &cfg) {
+    static const int cap = resident_grid((const void *)k_oneshot_a2a, cfg);
+    return launch_table(k_oneshot_a2a, a, cfg.grid < cap ? cfg.grid : cap, kThreads, cfg.stream);
+}
 int launch_oneshot_gv(const GvArgs &a, const LaunchCfg &cfg) {
     static const int cap = resident_grid((const void *)k_oneshot_gv, cfg);
-    const int g = cfg.grid < cap ? cfg.grid : cap;
-    hipLaunchKernelGGL(k_oneshot_gv, dim3(g), dim3(kThreads), 0, cfg.stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+    return launch_table(k_oneshot_gv, a, cfg.grid < cap ? cfg.grid : cap, kThreads, cfg.stream);
 }
-
+int launch_pipe_a2a(const A2AArgs &a, const LaunchCfg &cfg) {
+    return launch_table(k_pipe_a2a, a, cfg.grid, kPipeThreads, cfg.stream);
+}
 int launch_pipe_gv(const GvArgs &a, const LaunchCfg &cfg) {
-    hipLaunchKernelGGL(k_pipe_gv, dim3(cfg.grid), dim3(kPipeThreads), 0, cfg.stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : E_INTERN;
+    return launch_table(k_pipe_gv, a, cfg.grid, kPipeThreads, cfg.stream);
 }
 
 }  // namespace mv2

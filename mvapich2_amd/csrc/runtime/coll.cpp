@@ -1,6 +1,6 @@
 // coll.cpp — the mv2h_* C-ABI (include/mv2h.h): the op layer's entry points.  The collectives
-// themselves are coll_node.cpp (this node's ranks) and coll_mn.cpp (a job on several nodes); the
-// entry points here choose between the two.
+// themselves are coll_node.cpp and coll_table.cpp (this node's ranks) and coll_mn.cpp (a job on
+// several nodes); the entry points here choose between the two.
 #include <hip/hip_runtime.h>
 #include <string.h>
 

@@ -1,6 +1,8 @@
 // coll_internal.h — what the files of the collective runtime share: call.cpp (a call's stream,
-// timing marks, completion and error word), coll_node.cpp (the one-node collectives), coll_mn.cpp
-// (across nodes), coll_init.cpp (MPI_Init's tuning and self-test), coll.cpp (the mv2h_* C-ABI).
+// timing marks, completion and error word), coll_node.cpp (the one-node collectives and the two
+// kernel families' per-call reservations), coll_table.cpp (the one-node calls that move a table of
+// per-rank blocks: all-to-all, gather, scatter, allgatherv), coll_mn.cpp (across nodes),
+// coll_init.cpp (MPI_Init's tuning and self-test), coll.cpp (the mv2h_* C-ABI).
 #pragma once
 #include "world.h"
 
@@ -40,7 +42,84 @@ int reduce_entry(const void *sendbuf, void *recvbuf, size_t count, int dtype, in
 int reduce_scatter_entry(const void *sendbuf, void *recvbuf, const size_t *recvcounts, int dtype, int op, void *stream);
 int allgather_node(const void *sendbuf, void *recvbuf, size_t bytes, void *stream);
 int bcast_node(void *buffer, size_t bytes, int root, void *stream);
-// MPI_Alltoall / MPI_Alltoallv over this node's ranks (kernels: coll/alltoall.hip)
+// what coll_table.cpp launches with
+int grid_cap();
+LaunchCfg coll_cfg(int grid, hipStream_t st);
+struct PipeGeom {
+    int grid;
+    size_t tsub, tseg;
+    int nrounds;
+};
+PipeGeom pipe_geom(size_t maxlen);
+int oneshot_grid(size_t nvec, int gcap);
+int require_world();
+void *call_scratch(int idx, size_t bytes);
+// blocks of any size up to this move byte by byte through a one-shot kernel (allgather, the tables)
+constexpr size_t kOneShotBytewise = 2048;
+
+// The per-call reservation of each kernel family, over any argument struct that names the fields
+// alike (PipeArgs, OneShotArgs, coll/alltoall.h TableRt).  Nothing else advances w.round, w.epoch
+// and w.os_calls, so every rank advances them alike whatever mix of collectives it runs; on the
+// graph lane the kernel reads them from the device and the host advances nothing.
+// Pipelined: g.nrounds rounds of slot parities, 2 * g.nrounds flag epochs (the AG region's peers;
+// run_pipe adds the RS region's).
+template <class A>
+void pipe_reserve(A &a, const PipeGeom &g, hipStream_t st) {
+    World &w = world();
+    a.tsub = g.tsub;
+    a.tseg = g.tseg;
+    a.nrounds = g.nrounds;
+    a.rnt = w.pipe_rnt;
+    if (w.graph) {  // graph lane: own arenas and flags
+        a.ag_peer = w.g_peer_ag;
+        a.sig_peer = w.g_peer_sig;
+        a.sig_own = w.g_sig;
+        a.dseq = w.dseq;
+    } else {
+        a.ag_peer = w.peer_ag;
+        a.sig_peer = w.peer_sig;
+        a.sig_own = w.sig;
+        a.round0 = w.round;
+        w.round += (uint64_t)g.nrounds;
+        a.epoch0 = w.epoch + 1;
+        w.epoch += 2 * (uint64_t)g.nrounds;
+        log_epochs(a.epoch0, w.epoch, st);
+    }
+    a.err = w.h_err;
+    a.timeout = w.timeout_ticks;
+    a.light = w.light_release;
+    a.done = arm_done(st);
+}
+// One-shot: this call's arena half and flag epoch (`epoch`: the struct's member for it), the
+// peers, the error word, the completion word.
+template <class A>
+void oneshot_reserve(A &a, uint64_t &epoch, hipStream_t st) {
+    World &w = world();
+    const size_t half = (size_t)kMaxRanks * w.slot_bytes;
+    if (w.graph) {  // graph lane: the kernel picks the half and the epoch from the device
+        for (int j = 0; j < w.size; ++j) a.arena_peer.p[j] = w.g_peer_arena[j];
+        a.arena_own = w.g_arena;
+        a.sig_peer = w.g_peer_sig;
+        a.sig_own = w.g_sig;
+        a.dseq = w.dseq;
+        a.half = half;
+    } else {
+        const size_t par = (w.os_calls++ & 1) * half;
+        for (int j = 0; j < w.size; ++j) a.arena_peer.p[j] = w.peer_arena[j] + par;
+        a.arena_own = w.arena + par;
+        a.sig_peer = w.peer_sig;
+        a.sig_own = w.sig;
+        epoch = ++w.epoch;
+        log_epochs(epoch, epoch, st);
+    }
+    a.slot_bytes = w.slot_bytes;
+    a.err = w.h_err;
+    a.timeout = w.timeout_ticks;
+    a.light = w.light_release;
+    a.done = arm_done(st);
+}
+
+// ---- coll_table.cpp: the table collectives over this node's ranks (kernels: coll/alltoall.hip) ----
 int alltoall_node(const void *sendbuf, void *recvbuf, size_t bytes, void *stream);
 int alltoallv_node(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, const size_t *rbytes,
                    const size_t *roffs, void *stream);

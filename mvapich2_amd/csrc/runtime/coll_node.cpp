@@ -16,7 +16,6 @@
 #include <algorithm>
 
 #include "../../../include/mv2h.h"
-#include "../coll/alltoall.h"
 #include "coll_internal.h"
 #include "log.h"
 #include "pvars.h"
@@ -117,7 +116,7 @@ void log_plan(const char *coll, const Plan &p, size_t count) {
               p.inner ? algo_name(p.inner) : "");
 }
 
-static int grid_cap() {
+int grid_cap() {
     World &w = world();
     int g = w.max_grid / (w.nshare > 0 ? w.nshare : 1);
     if (g < 1) g = 1;
@@ -127,7 +126,7 @@ static int grid_cap() {
 
 // launch config of a collective kernel: identical on every rank (the grid
 // must match across ranks: workgroup b of each rank pairs with workgroup b)
-static LaunchCfg coll_cfg(int grid, hipStream_t st) {
+LaunchCfg coll_cfg(int grid, hipStream_t st) {
     World &w = world();
     LaunchCfg c{grid, 2, st};
     c.cus = w.cus;
@@ -146,16 +145,10 @@ long rs_scalar_max() { static const long v = env_long_coll("MV2AMD_RS_SCALAR_MAX
 // ---------------------------------------------------------------------------
 // pipelined collectives (coll/pipe.h)
 // ---------------------------------------------------------------------------
-struct PipeGeom {
-    int grid;
-    size_t tsub, tseg;
-    int nrounds;
-};
-
 // Grid and per-block range of a pipelined call.  A pure function of the
 // message geometry and of values every rank shares (CU count, ranks per GPU,
 // tuning knobs), so block b of every rank handles the same bytes.
-static PipeGeom pipe_geom(size_t maxlen) {
+PipeGeom pipe_geom(size_t maxlen) {
     World &w = world();
     int cap = std::min(kPipeMaxGrid, xcd_fair_cap(1, w.cus, w.nshare));  // k_pipe: one block per CU
     cap = std::min(cap, std::max(1, w.pipe_grid));
@@ -192,7 +185,7 @@ static void even_segments(PipeArgs &a, size_t bytes, int n) {
     }
 }
 
-// Fill the runtime part of `a`, reserve rounds/epochs and launch (no sync).
+// Fill the runtime part of `a`, reserve rounds/epochs (pipe_reserve) and launch (no sync).
 // dt == nullptr: data-movement modes (AG / BC).
 static int run_pipe(PipeArgs &a, int oi, const DtypeInfo *dt, hipStream_t st) {
     World &w = world();
@@ -202,31 +195,8 @@ static int run_pipe(PipeArgs &a, int oi, const DtypeInfo *dt, hipStream_t st) {
     for (int j = 0; j < a.n; ++j) maxlen = std::max(maxlen, a.seg_len[j]);
     if (maxlen == 0) return 0;  // every rank sees the same geometry
     const PipeGeom g = pipe_geom(maxlen);
-    a.tsub = g.tsub;
-    a.tseg = g.tseg;
-    a.nrounds = g.nrounds;
-    a.rnt = w.pipe_rnt;
-    if (w.graph) {  // graph lane: own arenas and flags; epochs and parities from the device
-        a.rs_peer = w.g_peer_rs;
-        a.ag_peer = w.g_peer_ag;
-        a.sig_peer = w.g_peer_sig;
-        a.sig_own = w.g_sig;
-        a.dseq = w.dseq;
-    } else {
-        a.rs_peer = w.peer_rs;
-        a.ag_peer = w.peer_ag;
-        a.sig_peer = w.peer_sig;
-        a.sig_own = w.sig;
-        a.round0 = w.round;
-        w.round += (uint64_t)g.nrounds;
-        a.epoch0 = w.epoch + 1;
-        w.epoch += 2 * (uint64_t)g.nrounds;
-        log_epochs(a.epoch0, w.epoch, st);
-    }
-    a.err = w.h_err;
-    a.timeout = w.timeout_ticks;
-    a.light = w.light_release;
-    a.done = arm_done(st);
+    a.rs_peer = w.graph ? w.g_peer_rs : w.peer_rs;
+    pipe_reserve(a, g, st);
     MV2_DEBUG("pipe mode %d grid %d tsub %zu rounds %d maxlen %zu", a.mode, g.grid, g.tsub, g.nrounds, maxlen);
     LaunchCfg cfg = coll_cfg(g.grid, st);
     tmark0(st);
@@ -235,41 +205,17 @@ static int run_pipe(PipeArgs &a, int oi, const DtypeInfo *dt, hipStream_t st) {
     return rc;
 }
 
-// The one-shot kernels' per-call part: this call's arena half and flag epoch (or, on the graph
-// lane, where the kernel reads them), the peers, the error word, the completion word.
+// The one-shot kernels' per-call part (oneshot_reserve) and the ranks.
 static void oneshot_common(OneShotArgs &a, hipStream_t st) {
-    World &w = world();
-    const int n = w.size;
-    const size_t half = (size_t)kMaxRanks * w.slot_bytes;
-    if (w.graph) {  // graph lane: the kernel picks the half and the epoch from the device
-        for (int j = 0; j < n; ++j) a.arena_peer.p[j] = w.g_peer_arena[j];
-        a.arena_own = w.g_arena;
-        a.sig_peer = w.g_peer_sig;
-        a.sig_own = w.g_sig;
-        a.dseq = w.dseq;
-        a.half = half;
-    } else {
-        const size_t par = (w.os_calls++ & 1) * half;
-        for (int j = 0; j < n; ++j) a.arena_peer.p[j] = w.peer_arena[j] + par;
-        a.arena_own = w.arena + par;
-        a.sig_peer = w.peer_sig;
-        a.sig_own = w.sig;
-        a.epoch = ++w.epoch;
-        log_epochs(a.epoch, a.epoch, st);
-    }
-    a.slot_bytes = w.slot_bytes;
-    a.n = n;
-    a.me = w.rank;
-    a.err = w.h_err;
-    a.timeout = w.timeout_ticks;
-    a.light = w.light_release;
-    a.done = arm_done(st);
+    a.n = world().size;
+    a.me = world().rank;
+    oneshot_reserve(a, a.epoch, st);
 }
 
 // one 16-B vector per thread of a 256-thread workgroup, up to 64 workgroups (256 KiB): the
 // one-shot kernels are latency-bound, and each further vector a thread owns costs it another
 // dependent memory round trip (MV2AMD_ONESHOT_VECS_PER_WG / _MAX_WG override)
-static int oneshot_grid(size_t nvec, int gcap) {
+int oneshot_grid(size_t nvec, int gcap) {
     static const long vpw = std::max(64L, env_long_coll("MV2AMD_ONESHOT_VECS_PER_WG", 256));
     static const int wmax = (int)std::min(1024L, std::max(1L, env_long_coll("MV2AMD_ONESHOT_MAX_WG", 64)));
     const int g = (int)((nvec + vpw - 1) / vpw);
@@ -289,7 +235,7 @@ static int oneshot_launch(const OneShotArgs &a, size_t nvec, int oi, const Dtype
 // ---------------------------------------------------------------------------
 // the collectives
 // ---------------------------------------------------------------------------
-static int require_world() {
+int require_world() {
     World &w = world();
     if (!w.inited) {
         MV2_ERR("collective called before MPI_Init");
@@ -314,7 +260,7 @@ struct Staged {
 // Device staging space of a call.  A captured call (graph lane) cannot use the shared scratch
 // buffers — a graph keeps their addresses for every replay while later calls regrow or reuse
 // them — so it takes a private piece of a pool that lives until MPI_Finalize.
-static void *call_scratch(int idx, size_t bytes) {
+void *call_scratch(int idx, size_t bytes) {
     World &w = world();
     if (!w.graph) return get_scratch(idx, bytes);
     const size_t need = (bytes + 255) & ~(size_t)255;
@@ -779,7 +725,6 @@ int allgather_node(const void *sendbuf, void *recvbuf, size_t bytes, void *strea
     // node's shared limits, so every rank makes it alike).  Whole 16-byte vectors move as vectors;
     // a block of up to kOneShotBytewise bytes of any other size moves byte by byte (osu_allgather
     // 8 B at 2 shared ranks: 15.6 us through the pipelined kernel)
-    constexpr size_t kOneShotBytewise = 2048;
     const bool vec = bytes % 16 == 0;
     if ((vec || bytes <= kOneShotBytewise) && bytes <= std::min(w.oneshot_max, w.slot_bytes)) {
         // blocks packed at `bytes` in dst (the scratch block holds pitch * n >= bytes * n)
@@ -897,586 +842,6 @@ int node_allreduce_intra(const void *sendbuf, void *recvbuf, size_t count, int d
     if (rc) return rc;
     log_plan("allreduce (node step)", p, count);
     return allreduce_impl(sendbuf, recvbuf, count, dt, oi, pick_stream(stream), tree_from_plan(p, n, count, me));
-}
-
-// ---------------------------------------------------------------------------
-// MPI_Alltoall / MPI_Alltoallv (kernels: coll/alltoall.hip).
-//
-// Both calls end in the same launch: a table of what this rank sends to and receives from every
-// rank (offset, length, and the misalignment each incoming block carries), moved by the one-shot
-// kernel when every pair is small and by the pipelined kernel otherwise.  The path, the grid and
-// the round count read only values every rank shares: for MPI_Alltoall the block size, for
-// MPI_Alltoallv the whole matrix of pair lengths, which the ranks publish in the control segment
-// and read behind a host barrier (send counts are local knowledge; the longest pair of the job
-// decides the geometry).
-// ---------------------------------------------------------------------------
-static uint64_t g_a2a_paths[4];  // calls by path (a2a_path_calls)
-static uint64_t g_a2a_seq;       // MPI_Alltoallv calls issued (the published rows' sequence number)
-uint64_t a2a_path_calls(int which) { return which >= 0 && which < 4 ? g_a2a_paths[which] : 0; }
-
-// blocks of any size up to this move byte by byte through the one-shot kernel (allgather_node's limit)
-constexpr size_t kA2ABytewise = 2048;
-
-// Path and geometry from the longest pair, whether every pair is a whole number of 16-byte
-// vectors on 16-byte offsets, and the node's shared limits.
-static A2APlan plan_from(size_t maxlen, bool vec) {
-    World &w = world();
-    A2APlan p{};
-    p.maxlen = maxlen;
-    if (!maxlen) return p;
-    if ((vec || maxlen <= kA2ABytewise) && maxlen <= std::min(w.oneshot_max, w.slot_bytes)) {
-        p.path = vec ? A2A_ONESHOT_VEC : A2A_ONESHOT_BYTES;
-        p.grid = oneshot_grid(vec ? maxlen / 16 : 0, grid_cap());
-        p.nrounds = 1;
-    } else {
-        const PipeGeom g = pipe_geom(maxlen);
-        p.path = A2A_PIPE;
-        p.grid = g.grid;
-        p.nrounds = g.nrounds;
-    }
-    return p;
-}
-
-int alltoallv_plan(int n, const size_t *slen, const size_t *rlen, const unsigned char *al16, A2APlan *out) {
-    size_t maxlen = 0;
-    bool vec = true, trunc = false;
-    for (int i = 0; i < n; ++i) {
-        vec = vec && al16[i];
-        for (int j = 0; j < n; ++j) {
-            trunc = trunc || slen[i * n + j] != rlen[j * n + i];
-            maxlen = std::max(maxlen, slen[i * n + j]);
-            vec = vec && slen[i * n + j] % 16 == 0;
-        }
-    }
-    if (trunc) return E_TRUNCATE;
-    *out = plan_from(maxlen, vec);
-    return 0;
-}
-
-// The per-call part of a table launch, shared by the all-to-all and the gather tables (A2AArgs /
-// GvArgs name these fields alike): the pipelined path takes its rounds and epochs, the one-shot
-// path its arena half and epoch, as every other collective reserves them, so every rank advances
-// w.epoch, w.round and w.os_calls alike.  Returns the grid.
-template <class Args>
-static int table_reserve(Args &a, const A2APlan &p, hipStream_t st) {
-    World &w = world();
-    a.n = w.size;
-    a.me = w.rank;
-    if (p.path == A2A_PIPE) {
-        // rounds and epochs exactly as run_pipe reserves them (it launches what it reserves, so the
-        // lines are restated here): nrounds rounds of slot parities, 2 * nrounds flag epochs
-        const PipeGeom g = pipe_geom(p.maxlen);
-        a.tseg = g.tseg;
-        a.tsub = g.tsub;
-        a.nrounds = g.nrounds;
-        a.rnt = w.pipe_rnt;
-        if (w.graph) {  // graph lane: own arenas and flags; epochs and parities from the device
-            a.ag_peer = w.g_peer_ag;
-            a.sig_peer = w.g_peer_sig;
-            a.sig_own = w.g_sig;
-            a.dseq = w.dseq;
-        } else {
-            a.ag_peer = w.peer_ag;
-            a.sig_peer = w.peer_sig;
-            a.sig_own = w.sig;
-            a.round0 = w.round;
-            w.round += (uint64_t)g.nrounds;
-            a.epoch0 = w.epoch + 1;
-            w.epoch += 2 * (uint64_t)g.nrounds;
-            log_epochs(a.epoch0, w.epoch, st);
-        }
-        a.err = w.h_err;
-        a.timeout = w.timeout_ticks;
-        a.light = w.light_release;
-        a.done = arm_done(st);
-        return g.grid;
-    }
-    OneShotArgs o{};
-    oneshot_common(o, st);
-    a.arena_peer = o.arena_peer;
-    a.arena_own = o.arena_own;
-    a.slot_bytes = o.slot_bytes;
-    a.half = o.half;
-    a.sig_peer = o.sig_peer;
-    a.sig_own = o.sig_own;
-    a.epoch0 = o.epoch;
-    a.light = o.light;
-    a.err = o.err;
-    a.timeout = o.timeout;
-    a.done = o.done;
-    a.dseq = o.dseq;
-    a.nvec = p.path == A2A_ONESHOT_VEC ? p.maxlen / 16 : 0;
-    return p.grid;
-}
-
-// Launch the planned kernel on the table in `a` (send / recv 16-byte aligned device memory, or any
-// device memory on the byte-wise path).
-static int a2a_launch(A2AArgs &a, const A2APlan &p, hipStream_t st) {
-    World &w = world();
-    bool shifted = false;
-    for (int j = 0; j < w.size; ++j)
-        shifted = shifted || (j != w.rank && a.rlen[j] && a.smis[j] != (uint32_t)(a.roff[j] & 15));
-    const int grid = table_reserve(a, p, st);
-    int rc;
-    if (p.path == A2A_PIPE) {
-        ++g_a2a_paths[2];
-        if (shifted) ++g_a2a_paths[3];
-        MV2_DEBUG("alltoall pipelined grid %d tsub %zu rounds %d maxlen %zu%s", grid, a.tsub, a.nrounds, p.maxlen,
-                  shifted ? " (shifted gather)" : "");
-        tmark0(st);
-        rc = launch_pipe_a2a(a, coll_cfg(grid, st));
-        tmark1(st);
-    } else {
-        ++g_a2a_paths[p.path == A2A_ONESHOT_VEC ? 0 : 1];
-        tmark0(st);
-        rc = launch_oneshot_a2a(a, coll_cfg(grid, st));
-        tmark1(st);
-    }
-    return rc;
-}
-
-int alltoall_node(const void *sendbuf, void *recvbuf, size_t bytes, void *stream) {
-    hp_entry();
-    int rc;
-    if ((rc = require_world())) return rc;
-    if (bytes == 0) return 0;
-    World &w = world();
-    hipStream_t st = pick_stream(stream);
-    const int n = w.size, me = w.rank;
-    const bool in_place = sendbuf == (const void *)-1;
-    if (n == 1) {
-        if (!in_place && hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDefault, st) != hipSuccess) return E_INTERN;
-        return finish(st, false);
-    }
-    const size_t total = bytes * (size_t)n;
-    const A2APlan p = plan_from(bytes, bytes % 16 == 0);
-    // Blocks lie back to back, so block j starts at j * bytes whatever that is modulo 16: only a
-    // base that is not 16-byte aligned (or host memory) is staged.  The byte-wise path reads its
-    // send buffer byte by byte and takes any device address.
-    const bool direct = is_device(recvbuf) && (uintptr_t)recvbuf % 16 == 0;
-    char *dst = direct ? (char *)recvbuf : (char *)call_scratch(1, total);
-    if (!dst) return E_NO_MEM;
-    if (in_place && !direct) hipMemcpyAsync(dst, recvbuf, total, hipMemcpyDefault, st);
-    const char *src = dst;
-    if (!in_place) {
-        src = (const char *)sendbuf;
-        if (!(is_device(sendbuf) && (p.path == A2A_ONESHOT_BYTES || (uintptr_t)sendbuf % 16 == 0))) {
-            char *t = (char *)call_scratch(0, total);
-            if (!t) return E_NO_MEM;
-            beacon(BC_STAGE);
-            hipMemcpyAsync(t, sendbuf, total, hipMemcpyDefault, st);
-            src = t;
-        }
-    }
-    A2AArgs a{};
-    a.send = src;
-    a.recv = dst;
-    for (int j = 0; j < n; ++j) {
-        a.soff[j] = a.roff[j] = (size_t)j * bytes;
-        a.slen[j] = a.rlen[j] = bytes;
-        a.smis[j] = (uint32_t)(((size_t)me * bytes) & 15);  // rank j's block for me starts at me * bytes there
-    }
-    if ((rc = a2a_launch(a, p, st))) return rc;
-    if (!direct && enq_copy_last(recvbuf, dst, total, st) != hipSuccess) return E_INTERN;
-    return finish(st, w.timing);
-}
-
-// One table of per-pair blocks whose lengths only the two ends of a pair know (MPI_Alltoallv; the
-// root's row or column of MPI_Scatterv / MPI_Gatherv), n > 1: exchange the rows, plan from the
-// whole matrix, stage, launch, copy back.  in_place: the send blocks are the receive blocks
-// (sendbuf is not read).  A buffer none of whose blocks has a length is never dereferenced.
-static int a2av_table(const char *name, const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf,
-                      const size_t *rbytes, const size_t *roffs, bool in_place, hipStream_t st) {
-    World &w = world();
-    const int n = w.size, me = w.rank;
-    int rc;
-    // publish my row, meet, read the matrix, meet again (nobody rewrites its row for the next call
-    // before every rank has read this one)
-    A2ARow &mine = w.shm->a2a[me];
-    mine.seq = ++g_a2a_seq;
-    bool al16 = true;
-    size_t sspan = 0, rspan = 0;
-    for (int j = 0; j < n; ++j) {
-        mine.slen[j] = sbytes[j];
-        mine.rlen[j] = rbytes[j];
-        mine.smis[j] = (uint8_t)(soffs[j] & 15);
-        al16 = al16 && soffs[j] % 16 == 0 && roffs[j] % 16 == 0;
-        if (sbytes[j]) sspan = std::max(sspan, soffs[j] + sbytes[j]);
-        if (rbytes[j]) rspan = std::max(rspan, roffs[j] + rbytes[j]);
-    }
-    mine.al16 = al16;
-    host_barrier();
-    size_t slen[kMaxRanks * kMaxRanks], rlen[kMaxRanks * kMaxRanks];
-    unsigned char al[kMaxRanks];
-    uint32_t smis[kMaxRanks];
-    bool same_call = true;
-    for (int i = 0; i < n; ++i) {
-        const A2ARow &r = w.shm->a2a[i];
-        same_call = same_call && r.seq == mine.seq;
-        al[i] = r.al16;
-        smis[i] = r.smis[me];
-        for (int j = 0; j < n; ++j) {
-            slen[i * n + j] = (size_t)r.slen[j];
-            rlen[i * n + j] = (size_t)r.rlen[j];
-        }
-    }
-    host_barrier();
-    if (!same_call) {
-        MV2_ERR("%s: the ranks of the node are not in the same call", name);
-        return E_OTHER;
-    }
-    A2APlan p{};
-    if ((rc = alltoallv_plan(n, slen, rlen, al, &p))) {
-        MV2_ERR("%s: a pair's send and receive lengths differ", name);
-        return rc;
-    }
-    if (p.path == A2A_NONE) return 0;  // every pair is empty, on every rank
-    // Staging.  Only bytes of receive blocks may be written, so a staged receive buffer is copied
-    // back block by block; the send side is staged block by block too (a gap need not be readable).
-    const bool bytewise = p.path == A2A_ONESHOT_BYTES;
-    const bool direct = is_device(recvbuf) && (bytewise || (uintptr_t)recvbuf % 16 == 0);
-    char *dst = direct ? (char *)recvbuf : (char *)call_scratch(1, std::max<size_t>(rspan, 16));
-    if (!dst) return E_NO_MEM;
-    const char *src = dst;
-    if (in_place) {
-        if (!direct)
-            for (int j = 0; j < n; ++j)
-                if (rbytes[j]) hipMemcpyAsync(dst + roffs[j], (char *)recvbuf + roffs[j], rbytes[j], hipMemcpyDefault, st);
-    } else if (is_device(sendbuf) && (bytewise || (uintptr_t)sendbuf % 16 == 0)) {
-        src = (const char *)sendbuf;
-    } else {
-        char *t = (char *)call_scratch(0, std::max<size_t>(sspan, 16));
-        if (!t) return E_NO_MEM;
-        beacon(BC_STAGE);
-        for (int j = 0; j < n; ++j)
-            if (sbytes[j]) hipMemcpyAsync(t + soffs[j], (const char *)sendbuf + soffs[j], sbytes[j], hipMemcpyDefault, st);
-        src = t;
-    }
-    A2AArgs a{};
-    a.send = src;
-    a.recv = dst;
-    for (int j = 0; j < n; ++j) {
-        a.soff[j] = soffs[j];
-        a.slen[j] = sbytes[j];
-        a.roff[j] = roffs[j];
-        a.rlen[j] = rbytes[j];
-        a.smis[j] = smis[j];
-    }
-    if ((rc = a2a_launch(a, p, st))) return rc;
-    if (!direct)
-        for (int j = 0; j < n; ++j)
-            if (rbytes[j] && enq_copy((char *)recvbuf + roffs[j], dst + roffs[j], rbytes[j], st) != hipSuccess)
-                return E_INTERN;
-    return finish(st, w.timing);
-}
-
-int alltoallv_node(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, const size_t *rbytes,
-                   const size_t *roffs, void *stream) {
-    hp_entry();
-    int rc;
-    if ((rc = require_world())) return rc;
-    if (!rbytes || !roffs) return E_ARG;
-    World &w = world();
-    const bool in_place = sendbuf == (const void *)-1;
-    if (in_place) {
-        sbytes = rbytes;
-        soffs = roffs;
-    } else if (!sbytes || !soffs) {
-        return E_ARG;
-    }
-    hipStream_t st = pick_stream(stream);
-    if (w.size == 1) {
-        if (sbytes[0] != rbytes[0]) return E_TRUNCATE;
-        if (!in_place && sbytes[0] &&
-            hipMemcpyAsync((char *)recvbuf + roffs[0], (const char *)sendbuf + soffs[0], sbytes[0], hipMemcpyDefault, st) !=
-                hipSuccess)
-            return E_INTERN;
-        return finish(st, false);
-    }
-    return a2av_table("MPI_Alltoallv", sendbuf, sbytes, soffs, recvbuf, rbytes, roffs, in_place, st);
-}
-
-// ---------------------------------------------------------------------------
-// MPI_Allgatherv / MPI_Gather(v) / MPI_Scatter(v) (kernels: coll/alltoall.hip).
-//
-// Allgatherv and Gather: every rank has one block for a set of ranks -- the gather table (GvArgs)
-// on k_oneshot_gv / k_pipe_gv, which read a block once and store it to every destination.  The
-// plan reads only the n block lengths, which every rank knows (Allgatherv's recvcounts, Gather's
-// one count); displacements and addresses are local and never enter it.  recvcounts that differ
-// between the ranks of one MPI_Allgatherv are erroneous MPI: the ranks then disagree on the grid
-// or the round count and the call ends in the kernels' timeout (MPI_ERR_OTHER).
-// Scatter: n different blocks at the root -- an all-to-all table whose only non-empty row is the
-// root's, on the all-to-all kernels.  A receiver derives the misalignment its block arrives with
-// from the root's 16-byte-aligned base: (me * bytes) & 15.
-// Gatherv and Scatterv: only the root knows the lengths, so they are all-to-all tables with one
-// non-empty column / row through a2av_table (row exchange, MPI_ERR_TRUNCATE for a mismatched pair
-// on every rank before any device work), on the all-to-all kernels and under their counters.
-// ---------------------------------------------------------------------------
-static uint64_t g_gv_paths[4];  // calls by path (gv_path_calls)
-static int g_agv_via_a2a;       // test hook: MPI_Allgatherv through the all-to-all table
-uint64_t gv_path_calls(int which) { return which >= 0 && which < 4 ? g_gv_paths[which] : 0; }
-void set_agv_via_a2a(int on) { g_agv_via_a2a = on != 0; }
-
-int gv_plan(int n, const size_t *len, A2APlan *out) {
-    size_t maxlen = 0;
-    bool vec = true;
-    for (int j = 0; j < n; ++j) {
-        maxlen = std::max(maxlen, len[j]);
-        vec = vec && len[j] % 16 == 0;
-    }
-    *out = plan_from(maxlen, vec);
-    return 0;
-}
-
-// One gather table, n > 1, planned: my block (slen bytes at sendbuf, any memory) goes to the ranks
-// of dmask (own bit: also to my own receive block); I gather rlens[j] bytes from rank j at recvbuf
-// + roffs[j] (all zero on a rank that receives nothing; its recvbuf is not dereferenced).  via_a2a:
-// the same table on the all-to-all kernels (soff[j] = 0 for every j).
-static int gv_run(const void *sendbuf, size_t slen, unsigned dmask, void *recvbuf, const size_t *roffs,
-                  const size_t *rlens, const A2APlan &p, bool via_a2a, hipStream_t st) {
-    World &w = world();
-    const int n = w.size, me = w.rank;
-    const bool bytewise = p.path == A2A_ONESHOT_BYTES, vecpath = p.path == A2A_ONESHOT_VEC;
-    if (!slen) dmask = 0;
-    if (!dmask) slen = 0;
-    const bool own = (dmask >> me) & 1u;
-    // wr[j]: bytes this call writes into my receive block j
-    size_t wr[kMaxRanks] = {}, off[kMaxRanks] = {}, total = 0;
-    bool offs16 = true;
-    for (int j = 0; j < n; ++j) {
-        wr[j] = j != me ? rlens[j] : (own ? slen : 0);
-        if (wr[j]) offs16 = offs16 && roffs[j] % 16 == 0;
-        total += (wr[j] + 15) & ~(size_t)15;
-    }
-    // Staging.  A vector path wants an aligned base (and, one-shot, aligned displacements): a rank
-    // whose own are not gathers into scratch at packed aligned offsets and copies out block by
-    // block, so only bytes of receive blocks are ever written.
-    const bool direct =
-        !total || (is_device(recvbuf) && (bytewise || ((uintptr_t)recvbuf % 16 == 0 && (!vecpath || offs16))));
-    char *dst = (char *)recvbuf;
-    if (!total) {
-        dst = nullptr;
-    } else if (direct) {
-        for (int j = 0; j < n; ++j) off[j] = wr[j] ? roffs[j] : 0;
-    } else {
-        if (!(dst = (char *)call_scratch(1, total))) return E_NO_MEM;
-        for (size_t j = 0, o = 0; j < (size_t)n; o += (wr[j] + 15) & ~(size_t)15, ++j) off[j] = o;
-    }
-    const char *src = nullptr;
-    if (slen) {
-        src = (const char *)sendbuf;
-        if (!(is_device(sendbuf) && (bytewise || (uintptr_t)sendbuf % 16 == 0))) {
-            char *t = (char *)call_scratch(0, slen);
-            if (!t) return E_NO_MEM;
-            beacon(BC_STAGE);
-            hipMemcpyAsync(t, sendbuf, slen, hipMemcpyDefault, st);
-            src = t;
-        }
-    }
-    int rc;
-    if (via_a2a) {
-        A2AArgs a{};
-        a.send = src;
-        a.recv = dst;
-        for (int j = 0; j < n; ++j) {
-            a.slen[j] = (dmask >> j) & 1u ? slen : 0;
-            a.roff[j] = off[j];
-            a.rlen[j] = wr[j];
-        }
-        if ((rc = a2a_launch(a, p, st))) return rc;
-    } else {
-        GvArgs a{};
-        a.send = src;
-        a.slen = slen;
-        a.dmask = dmask;
-        a.recv = dst;
-        bool shifted = false;
-        for (int j = 0; j < n; ++j) {
-            a.roff[j] = off[j];
-            a.rlen[j] = j != me ? wr[j] : 0;
-            shifted = shifted || (wr[j] && ((uintptr_t)(dst + off[j]) & 15));
-        }
-        const int grid = table_reserve(a, p, st);
-        tmark0(st);
-        if (p.path == A2A_PIPE) {
-            ++g_gv_paths[2];
-            if (shifted) ++g_gv_paths[3];
-            MV2_DEBUG("gather table pipelined grid %d tsub %zu rounds %d maxlen %zu mask %#x%s", grid, a.tsub, a.nrounds,
-                      p.maxlen, dmask, shifted ? " (shifted gather)" : "");
-            rc = launch_pipe_gv(a, coll_cfg(grid, st));
-        } else {
-            ++g_gv_paths[vecpath ? 0 : 1];
-            rc = launch_oneshot_gv(a, coll_cfg(grid, st));
-        }
-        tmark1(st);
-        if (rc) return rc;
-    }
-    if (!direct)
-        for (int j = 0; j < n; ++j)
-            if (wr[j] && enq_copy((char *)recvbuf + roffs[j], dst + off[j], wr[j], st) != hipSuccess) return E_INTERN;
-    return finish(st, w.timing);
-}
-
-int allgatherv_node(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes, const size_t *roffs,
-                    void *stream) {
-    hp_entry();
-    int rc;
-    if ((rc = require_world())) return rc;
-    if (!rbytes || !roffs) return E_ARG;
-    World &w = world();
-    const int n = w.size, me = w.rank;
-    const bool in_place = sendbuf == (const void *)-1;
-    if (!in_place && sbytes != rbytes[me]) return E_TRUNCATE;
-    A2APlan p{};
-    gv_plan(n, rbytes, &p);
-    if (p.path == A2A_NONE) return 0;  // every count is zero, on every rank
-    hipStream_t st = pick_stream(stream);
-    const size_t mine = rbytes[me];
-    const char *src = in_place ? (const char *)recvbuf + roffs[me] : (const char *)sendbuf;
-    if (n == 1) {
-        if (!in_place && hipMemcpyAsync((char *)recvbuf + roffs[0], src, mine, hipMemcpyDefault, st) != hipSuccess)
-            return E_INTERN;
-        return finish(st, false);
-    }
-    unsigned dmask = ((1u << n) - 1u) & ~(1u << me);
-    if (!in_place) dmask |= 1u << me;
-    return gv_run(src, mine, dmask, recvbuf, roffs, rbytes, p, g_agv_via_a2a != 0, st);
-}
-
-int gather_node(const void *sendbuf, void *recvbuf, size_t bytes, int root, void *stream) {
-    hp_entry();
-    int rc;
-    if ((rc = require_world())) return rc;
-    World &w = world();
-    const int n = w.size, me = w.rank;
-    if (root < 0 || root >= n) return E_ROOT;
-    if (bytes == 0) return 0;
-    hipStream_t st = pick_stream(stream);
-    const bool in_place = me == root && sendbuf == (const void *)-1;
-    if (n == 1) {
-        if (!in_place && hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDefault, st) != hipSuccess) return E_INTERN;
-        return finish(st, false);
-    }
-    size_t len[kMaxRanks], roffs[kMaxRanks] = {}, rlens[kMaxRanks] = {};
-    for (int j = 0; j < n; ++j) {
-        len[j] = bytes;
-        if (me == root) {
-            roffs[j] = (size_t)j * bytes;
-            rlens[j] = bytes;
-        }
-    }
-    A2APlan p{};
-    gv_plan(n, len, &p);
-    // the root's own block is copied by the own bit, or is in place: the root pushes nothing
-    const unsigned dmask = me == root ? (in_place ? 0u : 1u << me) : 1u << root;
-    return gv_run(in_place ? nullptr : sendbuf, bytes, dmask, me == root ? recvbuf : nullptr, roffs, rlens, p, false, st);
-}
-
-int gatherv_node(const void *sendbuf, size_t sbytes, void *recvbuf, const size_t *rbytes, const size_t *roffs, int root,
-                 void *stream) {
-    hp_entry();
-    int rc;
-    if ((rc = require_world())) return rc;
-    World &w = world();
-    const int n = w.size, me = w.rank;
-    if (root < 0 || root >= n) return E_ROOT;
-    if (me == root && (!rbytes || !roffs)) return E_ARG;
-    hipStream_t st = pick_stream(stream);
-    const bool in_place = me == root && sendbuf == (const void *)-1;
-    if (n == 1) {
-        if (in_place) return 0;
-        if (sbytes != rbytes[0]) return E_TRUNCATE;
-        if (sbytes && hipMemcpyAsync((char *)recvbuf + roffs[0], sendbuf, sbytes, hipMemcpyDefault, st) != hipSuccess)
-            return E_INTERN;
-        return finish(st, false);
-    }
-    size_t sb[kMaxRanks] = {}, so[kMaxRanks] = {}, rb[kMaxRanks] = {}, ro[kMaxRanks] = {};
-    if (me == root) {
-        for (int j = 0; j < n; ++j) {
-            rb[j] = rbytes[j];
-            ro[j] = rbytes[j] ? roffs[j] : 0;
-        }
-        if (in_place) rb[me] = ro[me] = 0;  // already there
-        else sb[me] = sbytes;
-    } else {
-        sb[root] = sbytes;
-    }
-    return a2av_table("MPI_Gatherv", in_place ? nullptr : sendbuf, sb, so, me == root ? recvbuf : nullptr, rb, ro, false, st);
-}
-
-int scatter_node(const void *sendbuf, void *recvbuf, size_t bytes, int root, void *stream) {
-    hp_entry();
-    int rc;
-    if ((rc = require_world())) return rc;
-    World &w = world();
-    const int n = w.size, me = w.rank;
-    if (root < 0 || root >= n) return E_ROOT;
-    if (bytes == 0) return 0;
-    hipStream_t st = pick_stream(stream);
-    const bool in_place = me == root && recvbuf == (void *)-1;
-    if (n == 1) {
-        if (!in_place && hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDefault, st) != hipSuccess) return E_INTERN;
-        return finish(st, false);
-    }
-    const A2APlan p = plan_from(bytes, bytes % 16 == 0);
-    const bool bytewise = p.path == A2A_ONESHOT_BYTES;
-    A2AArgs a{};
-    // my block arrives at recvbuf (the root's own: a local copy, unless it stays in place)
-    const bool direct = in_place || (is_device(recvbuf) && (bytewise || (uintptr_t)recvbuf % 16 == 0));
-    char *dst = in_place ? nullptr : (char *)recvbuf;
-    if (!direct && !(dst = (char *)call_scratch(1, bytes))) return E_NO_MEM;
-    a.recv = dst;
-    if (!in_place) a.rlen[root] = bytes;
-    a.smis[root] = (uint32_t)(((size_t)me * bytes) & 15);
-    if (me == root) {
-        const size_t total = bytes * (size_t)n;
-        const char *src = (const char *)sendbuf;
-        if (!(is_device(sendbuf) && (bytewise || (uintptr_t)sendbuf % 16 == 0))) {
-            char *t = (char *)call_scratch(0, total);
-            if (!t) return E_NO_MEM;
-            beacon(BC_STAGE);
-            hipMemcpyAsync(t, sendbuf, total, hipMemcpyDefault, st);
-            src = t;
-        }
-        a.send = src;
-        for (int j = 0; j < n; ++j) {
-            a.soff[j] = (size_t)j * bytes;
-            a.slen[j] = j == me && in_place ? 0 : bytes;
-        }
-    }
-    if ((rc = a2a_launch(a, p, st))) return rc;
-    if (!direct && enq_copy_last(recvbuf, dst, bytes, st) != hipSuccess) return E_INTERN;
-    return finish(st, w.timing);
-}
-
-int scatterv_node(const void *sendbuf, const size_t *sbytes, const size_t *soffs, void *recvbuf, size_t rbytes, int root,
-                  void *stream) {
-    hp_entry();
-    int rc;
-    if ((rc = require_world())) return rc;
-    World &w = world();
-    const int n = w.size, me = w.rank;
-    if (root < 0 || root >= n) return E_ROOT;
-    if (me == root && (!sbytes || !soffs)) return E_ARG;
-    hipStream_t st = pick_stream(stream);
-    const bool in_place = me == root && recvbuf == (void *)-1;
-    if (n == 1) {
-        if (in_place) return 0;
-        if (sbytes[0] != rbytes) return E_TRUNCATE;
-        if (rbytes && hipMemcpyAsync(recvbuf, (const char *)sendbuf + soffs[0], rbytes, hipMemcpyDefault, st) != hipSuccess)
-            return E_INTERN;
-        return finish(st, false);
-    }
-    size_t sb[kMaxRanks] = {}, so[kMaxRanks] = {}, rb[kMaxRanks] = {}, ro[kMaxRanks] = {};
-    if (me == root) {
-        for (int j = 0; j < n; ++j) {
-            sb[j] = sbytes[j];
-            so[j] = sbytes[j] ? soffs[j] : 0;
-        }
-        if (in_place) sb[me] = so[me] = 0;  // stays where it is
-    }
-    if (!in_place) rb[root] = rbytes;
-    return a2av_table("MPI_Scatterv", me == root ? sendbuf : nullptr, sb, so, in_place ? nullptr : recvbuf, rb, ro, false, st);
 }
 
 }  // namespace mv2

@@ -86,7 +86,7 @@ struct alignas(64) ShmRank {
     std::atomic<uint32_t> bh_pos;
 };
 
-// One rank's row of an MPI_Alltoallv (coll_node.cpp): what it sends to and expects from every rank
+// One rank's row of an MPI_Alltoallv (coll_table.cpp): what it sends to and expects from every rank
 // of the node, published for the call numbered `seq` so that every rank plans from the whole matrix
 struct A2ARow {
     uint64_t seq;
