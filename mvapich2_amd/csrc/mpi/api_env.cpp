@@ -1,0 +1,197 @@
+// api_env.cpp — environment, error handlers, communicator queries, MPI_Barrier and user ops
+// (api_internal.h has the front end's shared state and checks).
+#include <stdio.h>
+#include <stdlib.h>
+#include <time.h>
+#include <unistd.h>
+
+#include "../runtime/world.h"
+#include "api_internal.h"
+
+namespace mv2 {
+
+std::recursive_mutex g_cs;
+bool g_initialized = false, g_finalized = false;
+std::vector<UserOp> g_uops;
+
+static MPI_Errhandler g_eh[2] = {MPI_ERRORS_ARE_FATAL, MPI_ERRHANDLER_NULL};  // SELF: unset, WORLD's applies
+
+static const char *err_name(int c) {
+    switch (c) {
+    case MPI_SUCCESS: return "MPI_SUCCESS: no error";
+    case MPI_ERR_BUFFER: return "MPI_ERR_BUFFER: invalid buffer pointer";
+    case MPI_ERR_COUNT: return "MPI_ERR_COUNT: invalid count argument";
+    case MPI_ERR_TYPE: return "MPI_ERR_TYPE: invalid datatype";
+    case MPI_ERR_COMM: return "MPI_ERR_COMM: invalid communicator";
+    case MPI_ERR_ROOT: return "MPI_ERR_ROOT: invalid root";
+    case MPI_ERR_OP: return "MPI_ERR_OP: invalid reduce operation";
+    case MPI_ERR_ARG: return "MPI_ERR_ARG: invalid argument";
+    case MPI_ERR_TRUNCATE: return "MPI_ERR_TRUNCATE: message truncated";
+    case MPI_ERR_OTHER: return "MPI_ERR_OTHER: other error";
+    case MPI_ERR_INTERN: return "MPI_ERR_INTERN: internal error";
+    case MPI_ERR_NO_MEM: return "MPI_ERR_NO_MEM: out of memory";
+    case MPI_ERR_UNSUPPORTED_OPERATION: return "MPI_ERR_UNSUPPORTED_OPERATION: unsupported operation";
+    default: return "unknown error";
+    }
+}
+
+int err_report(MPI_Comm comm, int code, const char *fn) {
+    const int ci = comm_index(comm);
+    const MPI_Errhandler eh = ci >= 0 && g_eh[ci] != MPI_ERRHANDLER_NULL ? g_eh[ci] : g_eh[0];
+    if (eh == MPI_ERRORS_ARE_FATAL) {
+        fprintf(stderr, "[mv2amd rank %d] Fatal error in %s: %s\n", mv2h_rank(), fn, err_name(code));
+        fflush(stderr);
+        abort();
+    }
+    static const int verbose = [] {
+        const char *v = getenv("MV2AMD_ERR_VERBOSE");  // tests: name every error a call returns
+        return v && *v && *v != '0';
+    }();
+    if (verbose) {
+        fprintf(stderr, "[mv2amd rank %d] %s returned %s\n", mv2h_rank(), fn, err_name(code));
+        fflush(stderr);
+    }
+    return code;
+}
+
+}  // namespace mv2
+
+using namespace mv2;
+
+extern "C" {
+
+// ---------------------------------------------------------------- environment
+MPI_API(Init, int *, char ***) {
+    CsLock lk;
+    if (g_initialized) return err_return(MPI_COMM_WORLD, MPI_ERR_OTHER, "MPI_Init");
+    int rc = world_init();
+    if (rc) return err_return(MPI_COMM_WORLD, rc, "MPI_Init");
+    g_initialized = true;
+    return MPI_SUCCESS;
+}
+
+MPI_API(Init_thread, int *argc, char ***argv, int required, int *provided) {
+    int rc = PMPI_Init(argc, argv);
+    if (provided) *provided = required > MPI_THREAD_SERIALIZED ? MPI_THREAD_SERIALIZED : required;
+    return rc;
+}
+
+MPI_API(Finalize, void) {
+    CsLock lk;
+    world_finalize();
+    g_finalized = true;
+    return MPI_SUCCESS;
+}
+
+MPI_API(Initialized, int *flag) {
+    *flag = g_initialized ? 1 : 0;
+    return MPI_SUCCESS;
+}
+
+MPI_API(Finalized, int *flag) {
+    *flag = g_finalized ? 1 : 0;
+    return MPI_SUCCESS;
+}
+
+MPI_API(Abort, MPI_Comm, int errorcode) {
+    fprintf(stderr, "[mv2amd rank %d] MPI_Abort(%d)\n", mv2h_rank(), errorcode);
+    fflush(stderr);
+    _exit(errorcode ? errorcode : 1);
+}
+
+double MPI_Wtime(void) __attribute__((weak, alias("PMPI_Wtime")));
+double PMPI_Wtime(void) {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * ts.tv_nsec;
+}
+
+double MPI_Wtick(void) __attribute__((weak, alias("PMPI_Wtick")));
+double PMPI_Wtick(void) { return 1e-9; }
+
+MPI_API(Get_processor_name, char *name, int *len) {
+    gethostname(name, MPI_MAX_PROCESSOR_NAME);
+    name[MPI_MAX_PROCESSOR_NAME - 1] = 0;
+    *len = (int)strlen(name);
+    return MPI_SUCCESS;
+}
+
+MPI_API(Error_string, int code, char *s, int *len) {
+    snprintf(s, MPI_MAX_ERROR_STRING, "%s", err_name(code));
+    *len = (int)strlen(s);
+    return MPI_SUCCESS;
+}
+
+MPI_API(Error_class, int code, int *cls) {
+    *cls = code & 0x7f;
+    return MPI_SUCCESS;
+}
+
+MPI_API(Comm_set_errhandler, MPI_Comm comm, MPI_Errhandler eh) {
+    const int ci = comm_index(comm);
+    if (ci < 0) return MPI_ERR_COMM;
+    if (eh != MPI_ERRORS_ARE_FATAL && eh != MPI_ERRORS_RETURN) return MPI_ERR_ARG;
+    g_eh[ci] = eh;
+    return MPI_SUCCESS;
+}
+
+MPI_API(Errhandler_set, MPI_Comm comm, MPI_Errhandler eh) { return PMPI_Comm_set_errhandler(comm, eh); }
+
+MPI_API(Comm_get_errhandler, MPI_Comm comm, MPI_Errhandler *eh) {
+    const int ci = comm_index(comm);
+    if (ci < 0) return MPI_ERR_COMM;
+    *eh = g_eh[ci] == MPI_ERRHANDLER_NULL ? MPI_ERRORS_ARE_FATAL : g_eh[ci];  // comm_get_errhandler.c: unset reads FATAL
+    return MPI_SUCCESS;
+}
+
+// ---------------------------------------------------------------- communicators
+MPI_API(Comm_rank, MPI_Comm comm, int *rank) {
+    if (comm_index(comm) < 0) return err_return(comm, MPI_ERR_COMM, "MPI_Comm_rank");
+    *rank = comm_rank_of(comm);
+    return MPI_SUCCESS;
+}
+
+MPI_API(Comm_size, MPI_Comm comm, int *size) {
+    if (comm_index(comm) < 0) return err_return(comm, MPI_ERR_COMM, "MPI_Comm_size");
+    *size = comm_size_of(comm);
+    return MPI_SUCCESS;
+}
+
+MPI_API(Barrier, MPI_Comm comm) {
+    CsLock lk;
+    const int ci = comm_index(comm);
+    if (ci < 0) return err_return(comm, MPI_ERR_COMM, "MPI_Barrier");
+    if (ci == 0 && mv2h_barrier()) return err_return(comm, MPI_ERR_OTHER, "MPI_Barrier");
+    return MPI_SUCCESS;
+}
+
+// ---------------------------------------------------------------- user ops
+MPI_API(Op_create, MPI_User_function *fn, int commute, MPI_Op *op) {
+    CsLock lk;
+    if (!fn || !op) return err_return(MPI_COMM_WORLD, MPI_ERR_ARG, "MPI_Op_create");
+    g_uops.push_back(UserOp{fn, commute ? 1 : 0, true});
+    *op = kUserOpBase + (int)(g_uops.size() - 1);
+    return MPI_SUCCESS;
+}
+
+MPI_API(Op_free, MPI_Op *op) {
+    CsLock lk;
+    UserOp *u = op ? user_op(*op) : nullptr;
+    if (!u) return err_return(MPI_COMM_WORLD, MPI_ERR_OP, "MPI_Op_free");
+    u->live = false;
+    *op = MPI_OP_NULL;
+    return MPI_SUCCESS;
+}
+
+MPI_API(Op_commutative, MPI_Op op, int *commute) {
+    if (is_builtin_op(op)) {
+        *commute = 1;
+        return MPI_SUCCESS;
+    }
+    UserOp *u = user_op(op);
+    if (!u) return err_return(MPI_COMM_WORLD, MPI_ERR_OP, "MPI_Op_commutative");
+    *commute = u->commute;
+    return MPI_SUCCESS;
+}
+
+}  // extern "C"

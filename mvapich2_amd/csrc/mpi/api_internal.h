@@ -1,0 +1,133 @@
+// api_internal.h — what the files of the MPI-3.1 C front end (include/mpi.h over the mv2h C-ABI)
+// share: api_env.cpp (environment, error handlers, user ops), api_reduce.cpp (reductions),
+// api_move.cpp (data movement), api_request.cpp (requests, nonblocking collectives,
+// point-to-point).  Argument checking and error-handler behaviour follow the reference's MPI layer
+// (e.g. allreduce.c:827-960, reduce_local.c:206-268): count == 0 returns immediately, a predefined
+// op on a type outside its groups is MPI_ERR_OP, errors go through the communicator's error
+// handler (default MPI_ERRORS_ARE_FATAL).  Every MPI_X is a weak alias of PMPI_X
+// (allreduce.c:80-84).
+#pragma once
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "../../../include/mpi.h"
+#include "../../../include/mv2h.h"
+#include "../common.h"
+#include "datatype.h"
+
+// The two names of an entry point on one line, followed by the body of PMPI_<name>: MPI_<name> is
+// its weak alias.  Used inside extern "C".
+#define MPI_API(name, ...)                                                      \
+    int MPI_##name(__VA_ARGS__) __attribute__((weak, alias("PMPI_" #name)));    \
+    int PMPI_##name(__VA_ARGS__)
+#define MPIX_API(name, ...)                                                     \
+    int MPIX_##name(__VA_ARGS__) __attribute__((weak, alias("PMPIX_" #name)));  \
+    int PMPIX_##name(__VA_ARGS__)
+
+// the front end's own state and helpers: not exported from libmpi.so
+#define MV2_API_LOCAL __attribute__((visibility("hidden")))
+
+namespace mv2 {
+
+// ---- state (api_env.cpp), read and written under the global critical section
+extern MV2_API_LOCAL std::recursive_mutex g_cs;  // allreduce.c:838; recursive: MPI_I* locks, then calls the blocking entry
+extern MV2_API_LOCAL bool g_initialized, g_finalized;
+
+struct CsLock {
+    std::lock_guard<std::recursive_mutex> lk{g_cs};
+};
+
+struct UserOp {
+    MPI_User_function *fn;
+    int commute;
+    bool live;
+};
+extern MV2_API_LOCAL std::vector<UserOp> g_uops;
+constexpr int kUserOpBase = (int)0x98000000;  // direct-kind op handles (MPICH kind bits 10, object 0x18)
+
+static inline UserOp *user_op(MPI_Op op) {
+    const unsigned idx = (unsigned)(op - kUserOpBase);
+    if ((op & 0xff000000) != (kUserOpBase & 0xff000000) || idx >= g_uops.size() || !g_uops[idx].live) return nullptr;
+    return &g_uops[idx];
+}
+static inline bool op_valid(MPI_Op op) { return is_builtin_op(op) || user_op(op) != nullptr; }
+
+// ---- communicators
+static inline int comm_index(MPI_Comm c) {
+    if (c == MPI_COMM_WORLD) return 0;
+    if (c == MPI_COMM_SELF) return 1;
+    return -1;
+}
+static inline int comm_size_of(MPI_Comm comm) { return comm == MPI_COMM_SELF ? 1 : mv2h_size(); }
+static inline int comm_rank_of(MPI_Comm comm) { return comm == MPI_COMM_SELF ? 0 : mv2h_rank(); }
+
+// MPIR_Err_return_comm (allreduce.c:956, errutil.c:249-289): fatal handler aborts, return
+// handler passes the code; an invalid communicator, or one whose handler was never set
+// (MPI_COMM_SELF's until MPI_Comm_set_errhandler), takes MPI_COMM_WORLD's handler
+MV2_API_LOCAL int err_report(MPI_Comm comm, int code, const char *fn);
+static inline int err_return(MPI_Comm comm, int code, const char *fn) {
+    return code == MPI_SUCCESS ? code : err_report(comm, code, fn);
+}
+
+// The preamble of every call on a communicator: the library initialised and not finalized, then
+// the communicator; *n and *me, where asked for, are its size and this rank in it
+static inline int comm_checks(MPI_Comm comm, int *n = nullptr, int *me = nullptr) {
+    if (!g_initialized || g_finalized) return MPI_ERR_OTHER;
+    if (comm_index(comm) < 0) return MPI_ERR_COMM;
+    if (n) *n = comm_size_of(comm);
+    if (me) *me = comm_rank_of(comm);
+    return MPI_SUCCESS;
+}
+
+// ---- buffers
+static inline bool is_dev(const void *p) { return p && p != MPI_IN_PLACE && mv2h_is_device_ptr(p); }
+
+static inline bool is_x87(MPI_Datatype dt) {
+    return dt == MPI_LONG_DOUBLE || dt == MPI_C_LONG_DOUBLE_COMPLEX || dt == MPI_LONG_DOUBLE_INT;
+}
+
+// device or host memory on either side
+static inline int copy_any(void *d, const void *s, size_t bytes) {
+    if (!bytes || d == s) return MPI_SUCCESS;
+    return is_dev(d) || is_dev(s) ? mv2h_memcpy_dtod(d, s, bytes) : (memcpy(d, s, bytes), 0);
+}
+
+// the one-rank form of a stream-ordered call: a copy in stream order, device buffers only
+static inline int copy_any_enqueue(void *d, const void *s, size_t bytes, void *stream) {
+    if (s == MPI_IN_PLACE || s == d) return MPI_SUCCESS;
+    if (!is_dev(s) || !is_dev(d)) return MPI_ERR_ARG;
+    return mv2h_copy_enqueue(d, s, bytes, stream);
+}
+
+// The buffer checks of the reference's MPI layer, MPI_ERR_BUFFER each (mpierrs.h):
+// MPIR_ERRTEST_USERBUFFER (:313-331) — no buffer for count > 0 elements of a builtin type, or of
+// a derived type whose true lb is 0 and size > 0 (a null buffer is MPI_BOTTOM otherwise);
+// MPIR_ERRTEST_{SEND,RECV,}BUF_INPLACE (:274-301) — MPI_IN_PLACE where the call has no in-place
+// form; MPIR_ERRTEST_ALIAS_COLL (:132-140, MPIR_CVAR_COLL_ALIAS_CHECK's default 1) — the send
+// buffer is the receive buffer.
+static inline bool null_userbuf(const void *buf, long count, MPI_Datatype dt) {
+    if (count <= 0 || buf) return false;
+    return dtype_is_builtin(dt) || (dtype_valid(dt) && dtype_true_lb(dt) == 0 && dtype_size(dt) > 0);
+}
+static inline bool inplace_buf(const void *buf, long count) { return count > 0 && buf == MPI_IN_PLACE; }
+
+// ---- (count, type, committed)
+static inline int side_checks(long count, MPI_Datatype dt) {
+    if (count < 0) return MPI_ERR_COUNT;
+    if (!dtype_valid(dt) || !dtype_committed(dt)) return MPI_ERR_TYPE;
+    return MPI_SUCCESS;
+}
+
+// of the two sides of a call, each step on both sides before the next; MPI_IN_PLACE as the send
+// buffer takes the send side out
+static inline int pair_checks(bool in_place, long sendcount, MPI_Datatype sendtype, long recvcount,
+                              MPI_Datatype recvtype) {
+    if (recvcount < 0 || (!in_place && sendcount < 0)) return MPI_ERR_COUNT;
+    if (!dtype_valid(recvtype) || (!in_place && !dtype_valid(sendtype))) return MPI_ERR_TYPE;
+    if (!dtype_committed(recvtype) || (!in_place && !dtype_committed(sendtype))) return MPI_ERR_TYPE;
+    return MPI_SUCCESS;
+}
+
+}  // namespace mv2

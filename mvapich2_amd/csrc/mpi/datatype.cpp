@@ -22,6 +22,7 @@
 #include "../../../include/mv2h.h"
 #include "../common.h"
 #include "../runtime/world.h"
+#include "api_internal.h"
 
 namespace {
 
@@ -383,19 +384,16 @@ bool type_bounds(MPI_Datatype dt, long &lb, long &extent) {
 }
 }  // namespace
 
-#define WEAK(name) __attribute__((weak, alias("P" #name)))
-
 extern "C" {
 
-int PMPI_Type_size(MPI_Datatype dt, int *size) {
+MPI_API(Type_size, MPI_Datatype dt, int *size) {
     long s = dtype_size(dt);
     if (s < 0) return MPI_ERR_TYPE;
     *size = (int)s;
     return MPI_SUCCESS;
 }
-int MPI_Type_size(MPI_Datatype dt, int *size) WEAK(MPI_Type_size);
 
-int PMPI_Type_get_extent(MPI_Datatype dt, MPI_Aint *lb, MPI_Aint *extent) {
+MPI_API(Type_get_extent, MPI_Datatype dt, MPI_Aint *lb, MPI_Aint *extent) {
     long e = dtype_extent(dt);
     if (e < 0) return MPI_ERR_TYPE;
     Derived *d = derived(dt);
@@ -403,9 +401,8 @@ int PMPI_Type_get_extent(MPI_Datatype dt, MPI_Aint *lb, MPI_Aint *extent) {
     *extent = e;
     return MPI_SUCCESS;
 }
-int MPI_Type_get_extent(MPI_Datatype dt, MPI_Aint *lb, MPI_Aint *extent) WEAK(MPI_Type_get_extent);
 
-int PMPI_Type_get_true_extent(MPI_Datatype dt, MPI_Aint *tlb, MPI_Aint *text) {
+MPI_API(Type_get_true_extent, MPI_Datatype dt, MPI_Aint *tlb, MPI_Aint *text) {
     if (const mv2::DtypeInfo *b = mv2::dtype_lookup(dt)) {
         *tlb = 0;
         *text = b->size == b->extent ? b->extent : (dt == (int)0x8c000003 ? 8 : b->extent - 4);
@@ -417,9 +414,8 @@ int PMPI_Type_get_true_extent(MPI_Datatype dt, MPI_Aint *tlb, MPI_Aint *text) {
     *text = d->true_extent;
     return MPI_SUCCESS;
 }
-int MPI_Type_get_true_extent(MPI_Datatype dt, MPI_Aint *tlb, MPI_Aint *text) WEAK(MPI_Type_get_true_extent);
 
-int PMPI_Type_contiguous(int count, MPI_Datatype old, MPI_Datatype *nt) {
+MPI_API(Type_contiguous, int count, MPI_Datatype old, MPI_Datatype *nt) {
     if (count < 0) return MPI_ERR_COUNT;
     std::vector<Seg> s;
     long ext = 0, sz = 0;
@@ -428,25 +424,22 @@ int PMPI_Type_contiguous(int count, MPI_Datatype old, MPI_Datatype *nt) {
     for (int i = 0; i < count; ++i) offs.push_back((long)i * ext);
     return make_type(offs, 1, old, nt);
 }
-int MPI_Type_contiguous(int count, MPI_Datatype old, MPI_Datatype *nt) WEAK(MPI_Type_contiguous);
 
-int PMPI_Type_create_hvector(int count, int blocklen, MPI_Aint stride, MPI_Datatype old, MPI_Datatype *nt) {
+MPI_API(Type_create_hvector, int count, int blocklen, MPI_Aint stride, MPI_Datatype old, MPI_Datatype *nt) {
     if (count < 0) return MPI_ERR_COUNT;
     std::vector<long> offs;
     for (int i = 0; i < count; ++i) offs.push_back((long)i * stride);
     return make_type(offs, blocklen, old, nt);
 }
-int MPI_Type_create_hvector(int count, int blocklen, MPI_Aint stride, MPI_Datatype old, MPI_Datatype *nt) WEAK(MPI_Type_create_hvector);
 
-int PMPI_Type_vector(int count, int blocklen, int stride, MPI_Datatype old, MPI_Datatype *nt) {
+MPI_API(Type_vector, int count, int blocklen, int stride, MPI_Datatype old, MPI_Datatype *nt) {
     std::vector<Seg> s;
     long ext = 0, sz = 0;
     if (!type_segs(old, s, ext, sz)) return MPI_ERR_TYPE;
     return PMPI_Type_create_hvector(count, blocklen, (MPI_Aint)stride * ext, old, nt);
 }
-int MPI_Type_vector(int count, int blocklen, int stride, MPI_Datatype old, MPI_Datatype *nt) WEAK(MPI_Type_vector);
 
-int PMPI_Type_create_indexed_block(int count, int blocklen, const int displs[], MPI_Datatype old, MPI_Datatype *nt) {
+MPI_API(Type_create_indexed_block, int count, int blocklen, const int displs[], MPI_Datatype old, MPI_Datatype *nt) {
     if (count < 0) return MPI_ERR_COUNT;
     std::vector<Seg> s;
     long ext = 0, sz = 0;
@@ -455,18 +448,15 @@ int PMPI_Type_create_indexed_block(int count, int blocklen, const int displs[], 
     for (int i = 0; i < count; ++i) offs.push_back((long)displs[i] * ext);
     return make_type(offs, blocklen, old, nt);
 }
-int MPI_Type_create_indexed_block(int count, int blocklen, const int displs[], MPI_Datatype old, MPI_Datatype *nt) WEAK(MPI_Type_create_indexed_block);
 
-int PMPI_Type_create_hindexed_block(int count, int blocklen, const MPI_Aint displs[], MPI_Datatype old,
-                                    MPI_Datatype *nt) {
+MPI_API(Type_create_hindexed_block, int count, int blocklen, const MPI_Aint displs[], MPI_Datatype old,
+        MPI_Datatype *nt) {
     if (count < 0) return MPI_ERR_COUNT;
     std::vector<long> offs(displs, displs + count);
     return make_type(offs, blocklen, old, nt);
 }
-int MPI_Type_create_hindexed_block(int count, int blocklen, const MPI_Aint displs[], MPI_Datatype old,
-                                   MPI_Datatype *nt) WEAK(MPI_Type_create_hindexed_block);
 
-int PMPI_Type_indexed(int count, const int blocklens[], const int displs[], MPI_Datatype old, MPI_Datatype *nt) {
+MPI_API(Type_indexed, int count, const int blocklens[], const int displs[], MPI_Datatype old, MPI_Datatype *nt) {
     if (count < 0) return MPI_ERR_COUNT;
     long lb = 0, ext = 0;
     if (!type_bounds(old, lb, ext)) return MPI_ERR_TYPE;
@@ -474,21 +464,18 @@ int PMPI_Type_indexed(int count, const int blocklens[], const int displs[], MPI_
     for (int i = 0; i < count; ++i) blocks.push_back(Block{(long)displs[i] * ext, blocklens[i], old});
     return make_struct(blocks, nt);
 }
-int MPI_Type_indexed(int count, const int blocklens[], const int displs[], MPI_Datatype old, MPI_Datatype *nt) WEAK(MPI_Type_indexed);
 
-int PMPI_Type_create_hindexed(int count, const int blocklens[], const MPI_Aint displs[], MPI_Datatype old,
-                              MPI_Datatype *nt) {
+MPI_API(Type_create_hindexed, int count, const int blocklens[], const MPI_Aint displs[], MPI_Datatype old,
+        MPI_Datatype *nt) {
     if (count < 0) return MPI_ERR_COUNT;
     if (!dtype_valid(old)) return MPI_ERR_TYPE;
     std::vector<Block> blocks;
     for (int i = 0; i < count; ++i) blocks.push_back(Block{(long)displs[i], blocklens[i], old});
     return make_struct(blocks, nt);
 }
-int MPI_Type_create_hindexed(int count, const int blocklens[], const MPI_Aint displs[], MPI_Datatype old,
-                             MPI_Datatype *nt) WEAK(MPI_Type_create_hindexed);
 
-int PMPI_Type_create_struct(int count, const int blocklens[], const MPI_Aint displs[], const MPI_Datatype types[],
-                            MPI_Datatype *nt) {
+MPI_API(Type_create_struct, int count, const int blocklens[], const MPI_Aint displs[], const MPI_Datatype types[],
+        MPI_Datatype *nt) {
     if (count < 0) return MPI_ERR_COUNT;
     std::vector<Block> blocks;
     for (int i = 0; i < count; ++i) {
@@ -497,10 +484,8 @@ int PMPI_Type_create_struct(int count, const int blocklens[], const MPI_Aint dis
     }
     return make_struct(blocks, nt, true);
 }
-int MPI_Type_create_struct(int count, const int blocklens[], const MPI_Aint displs[], const MPI_Datatype types[],
-                           MPI_Datatype *nt) WEAK(MPI_Type_create_struct);
 
-int PMPI_Type_create_resized(MPI_Datatype old, MPI_Aint lb, MPI_Aint extent, MPI_Datatype *nt) {
+MPI_API(Type_create_resized, MPI_Datatype old, MPI_Aint lb, MPI_Aint extent, MPI_Datatype *nt) {
     std::vector<Block> one{Block{0, 1, old}};
     if (!dtype_valid(old)) return MPI_ERR_TYPE;
     std::lock_guard<std::recursive_mutex> lk(g_mu);
@@ -511,9 +496,8 @@ int PMPI_Type_create_resized(MPI_Datatype old, MPI_Aint lb, MPI_Aint extent, MPI
     d->extent = (long)extent;
     return MPI_SUCCESS;
 }
-int MPI_Type_create_resized(MPI_Datatype old, MPI_Aint lb, MPI_Aint extent, MPI_Datatype *nt) WEAK(MPI_Type_create_resized);
 
-int PMPI_Type_dup(MPI_Datatype old, MPI_Datatype *nt) {
+MPI_API(Type_dup, MPI_Datatype old, MPI_Datatype *nt) {
     long lb = 0, ext = 0;
     if (!type_bounds(old, lb, ext)) return MPI_ERR_TYPE;
     const int rc = PMPI_Type_create_resized(old, lb, ext, nt);
@@ -521,14 +505,13 @@ int PMPI_Type_dup(MPI_Datatype old, MPI_Datatype *nt) {
     if (!rc) derived(*nt)->committed = dtype_committed(old);
     return rc;
 }
-int MPI_Type_dup(MPI_Datatype old, MPI_Datatype *nt) WEAK(MPI_Type_dup);
 
 // Subarray (MPI-3.1 §4.1.3; the reference builds it from nested vectors,
 // create_subarray.c / dataloop pack_subarray kernel pack_unpack.cu:256):
 // one block per row of the fastest-varying dimension, then lb = 0 and
 // extent = prod(sizes) * extent(old).
-int PMPI_Type_create_subarray(int ndims, const int sizes[], const int subsizes[], const int starts[], int order,
-                              MPI_Datatype old, MPI_Datatype *nt) {
+MPI_API(Type_create_subarray, int ndims, const int sizes[], const int subsizes[], const int starts[], int order,
+        MPI_Datatype old, MPI_Datatype *nt) {
     if (ndims <= 0) return MPI_ERR_DIMS;
     if (order != MPI_ORDER_C && order != MPI_ORDER_FORTRAN) return MPI_ERR_ARG;
     long olb = 0, oext = 0;
@@ -568,10 +551,8 @@ int PMPI_Type_create_subarray(int ndims, const int sizes[], const int subsizes[]
     d->extent = total * oext;
     return MPI_SUCCESS;
 }
-int MPI_Type_create_subarray(int ndims, const int sizes[], const int subsizes[], const int starts[], int order,
-                             MPI_Datatype old, MPI_Datatype *nt) WEAK(MPI_Type_create_subarray);
 
-int PMPI_Type_commit(MPI_Datatype *dt) {
+MPI_API(Type_commit, MPI_Datatype *dt) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (dtype_is_builtin(*dt)) return MPI_SUCCESS;
     Derived *d = derived(*dt);
@@ -579,9 +560,8 @@ int PMPI_Type_commit(MPI_Datatype *dt) {
     d->committed = true;
     return MPI_SUCCESS;
 }
-int MPI_Type_commit(MPI_Datatype *dt) WEAK(MPI_Type_commit);
 
-int PMPI_Type_free(MPI_Datatype *dt) {
+MPI_API(Type_free, MPI_Datatype *dt) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     Derived *d = derived(*dt);
     if (!d) return MPI_ERR_TYPE;
@@ -590,21 +570,19 @@ int PMPI_Type_free(MPI_Datatype *dt) {
     *dt = MPI_DATATYPE_NULL;
     return MPI_SUCCESS;
 }
-int MPI_Type_free(MPI_Datatype *dt) WEAK(MPI_Type_free);
 
-int PMPI_Pack_size(int incount, MPI_Datatype dt, MPI_Comm, int *size) {
+MPI_API(Pack_size, int incount, MPI_Datatype dt, MPI_Comm, int *size) {
     long s = dtype_size(dt);
     if (s < 0) return MPI_ERR_TYPE;
     *size = (int)(s * incount);
     return MPI_SUCCESS;
 }
-int MPI_Pack_size(int incount, MPI_Datatype dt, MPI_Comm comm, int *size) WEAK(MPI_Pack_size);
 
 // Argument checks in pack.c:207-276's order: communicator, counts, null output buffer or
 // position (MPI_ERR_ARG), datatype valid and committed, then a packed size that does not fit
 // in outsize - *position: MPI_ERR_ARG (**argpackbuf), not MPI_ERR_TRUNCATE
-int PMPI_Pack(const void *inbuf, int incount, MPI_Datatype dt, void *outbuf, int outsize, int *position,
-              MPI_Comm comm) {
+MPI_API(Pack, const void *inbuf, int incount, MPI_Datatype dt, void *outbuf, int outsize, int *position,
+        MPI_Comm comm) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (comm != MPI_COMM_WORLD && comm != MPI_COMM_SELF) return MPI_ERR_COMM;
     if (incount < 0 || outsize < 0) return MPI_ERR_COUNT;
@@ -617,13 +595,12 @@ int PMPI_Pack(const void *inbuf, int incount, MPI_Datatype dt, void *outbuf, int
     if (!rc) *position += (int)(s * incount);
     return rc;
 }
-int MPI_Pack(const void *inbuf, int incount, MPI_Datatype dt, void *outbuf, int outsize, int *position, MPI_Comm comm) WEAK(MPI_Pack);
 
 // Argument checks of unpack.c:207-229: null input buffer (MPI_ERR_ARG), counts, communicator,
 // datatype valid and committed.  The reference does not check the packed size against insize
 // (its unpack reads past the buffer); here that is MPI_ERR_TRUNCATE.
-int PMPI_Unpack(const void *inbuf, int insize, int *position, void *outbuf, int outcount, MPI_Datatype dt,
-                MPI_Comm comm) {
+MPI_API(Unpack, const void *inbuf, int insize, int *position, void *outbuf, int outcount, MPI_Datatype dt,
+        MPI_Comm comm) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if ((insize > 0 && !inbuf) || !position) return MPI_ERR_ARG;
     if (insize < 0 || outcount < 0) return MPI_ERR_COUNT;
@@ -636,6 +613,5 @@ int PMPI_Unpack(const void *inbuf, int insize, int *position, void *outbuf, int 
     if (!rc) *position += (int)(s * outcount);
     return rc;
 }
-int MPI_Unpack(const void *inbuf, int insize, int *position, void *outbuf, int outcount, MPI_Datatype dt, MPI_Comm comm) WEAK(MPI_Unpack);
 
 }  // extern "C"

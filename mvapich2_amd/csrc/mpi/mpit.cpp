@@ -17,6 +17,7 @@
 #include "../../../include/mpi.h"
 #include "../runtime/orders.h"
 #include "../runtime/pvars.h"
+#include "api_internal.h"
 
 using namespace mv2;
 
@@ -148,45 +149,44 @@ std::string pvar_name(int index) {
 
 }  // namespace
 
-#define WEAK(name) __attribute__((weak, alias("P" #name)))
 #define REQUIRE_INIT()                                 \
     std::lock_guard<std::recursive_mutex> lk(g_mu);    \
     if (g_init <= 0) return MPI_T_ERR_NOT_INITIALIZED
 
 extern "C" {
 
-int PMPI_T_init_thread(int required, int *provided) {
+MPI_API(T_init_thread, int required, int *provided) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     (void)required;
     ++g_init;
     if (provided) *provided = MPI_THREAD_MULTIPLE;  // every entry takes the interface's lock
     return MPI_SUCCESS;
 }
-int PMPI_T_finalize(void) {
+MPI_API(T_finalize, void) {
     REQUIRE_INIT();
     --g_init;
     return MPI_SUCCESS;
 }
 
 // no enumerations are exported
-int PMPI_T_enum_get_info(MPI_T_enum, int *, char *, int *) {
+MPI_API(T_enum_get_info, MPI_T_enum, int *, char *, int *) {
     REQUIRE_INIT();
     return MPI_T_ERR_INVALID_HANDLE;
 }
-int PMPI_T_enum_get_item(MPI_T_enum, int, int *, char *, int *) {
+MPI_API(T_enum_get_item, MPI_T_enum, int, int *, char *, int *) {
     REQUIRE_INIT();
     return MPI_T_ERR_INVALID_HANDLE;
 }
 
 // ---- cvars ----
-int PMPI_T_cvar_get_num(int *num) {
+MPI_API(T_cvar_get_num, int *num) {
     REQUIRE_INIT();
     if (!num) return MPI_ERR_ARG;
     *num = kNumCvars;
     return MPI_SUCCESS;
 }
-int PMPI_T_cvar_get_info(int i, char *name, int *name_len, int *verbosity, MPI_Datatype *datatype,
-                         MPI_T_enum *enumtype, char *desc, int *desc_len, int *binding, int *scope) {
+MPI_API(T_cvar_get_info, int i, char *name, int *name_len, int *verbosity, MPI_Datatype *datatype,
+        MPI_T_enum *enumtype, char *desc, int *desc_len, int *binding, int *scope) {
     REQUIRE_INIT();
     if (i < 0 || i >= kNumCvars) return MPI_T_ERR_INVALID_INDEX;
     put_str(kCvars[i].name, name, name_len);
@@ -198,7 +198,7 @@ int PMPI_T_cvar_get_info(int i, char *name, int *name_len, int *verbosity, MPI_D
     if (scope) *scope = MPI_T_SCOPE_ALL_EQ;  // every rank must see the same value (checked at MPI_Init)
     return MPI_SUCCESS;
 }
-int PMPI_T_cvar_get_index(const char *name, int *index) {
+MPI_API(T_cvar_get_index, const char *name, int *index) {
     REQUIRE_INIT();
     if (!name || !index) return MPI_ERR_ARG;
     for (int i = 0; i < kNumCvars; ++i)
@@ -208,7 +208,7 @@ int PMPI_T_cvar_get_index(const char *name, int *index) {
         }
     return MPI_T_ERR_INVALID_NAME;
 }
-int PMPI_T_cvar_handle_alloc(int i, void *, MPI_T_cvar_handle *handle, int *count) {
+MPI_API(T_cvar_handle_alloc, int i, void *, MPI_T_cvar_handle *handle, int *count) {
     REQUIRE_INIT();
     if (i < 0 || i >= kNumCvars) return MPI_T_ERR_INVALID_INDEX;
     if (!handle || !count) return MPI_ERR_ARG;
@@ -216,14 +216,14 @@ int PMPI_T_cvar_handle_alloc(int i, void *, MPI_T_cvar_handle *handle, int *coun
     *count = 1;
     return MPI_SUCCESS;
 }
-int PMPI_T_cvar_handle_free(MPI_T_cvar_handle *handle) {
+MPI_API(T_cvar_handle_free, MPI_T_cvar_handle *handle) {
     REQUIRE_INIT();
     if (!handle || !*handle) return MPI_T_ERR_INVALID_HANDLE;
     delete *handle;
     *handle = MPI_T_CVAR_HANDLE_NULL;
     return MPI_SUCCESS;
 }
-int PMPI_T_cvar_read(MPI_T_cvar_handle handle, void *buf) {
+MPI_API(T_cvar_read, MPI_T_cvar_handle handle, void *buf) {
     REQUIRE_INIT();
     if (!handle) return MPI_T_ERR_INVALID_HANDLE;
     if (!buf) return MPI_ERR_ARG;
@@ -246,22 +246,22 @@ int PMPI_T_cvar_read(MPI_T_cvar_handle handle, void *buf) {
 }
 // the selection must be identical on every rank and is fixed at MPI_Init (the
 // environment is the way to set it)
-int PMPI_T_cvar_write(MPI_T_cvar_handle handle, const void *) {
+MPI_API(T_cvar_write, MPI_T_cvar_handle handle, const void *) {
     REQUIRE_INIT();
     if (!handle) return MPI_T_ERR_INVALID_HANDLE;
     return MPI_T_ERR_CVAR_SET_NEVER;
 }
 
 // ---- pvars ----
-int PMPI_T_pvar_get_num(int *num) {
+MPI_API(T_pvar_get_num, int *num) {
     REQUIRE_INIT();
     if (!num) return MPI_ERR_ARG;
     *num = (int)pvars().size();
     return MPI_SUCCESS;
 }
-int PMPI_T_pvar_get_info(int i, char *name, int *name_len, int *verbosity, int *var_class, MPI_Datatype *datatype,
-                         MPI_T_enum *enumtype, char *desc, int *desc_len, int *binding, int *readonly,
-                         int *continuous, int *atomic) {
+MPI_API(T_pvar_get_info, int i, char *name, int *name_len, int *verbosity, int *var_class, MPI_Datatype *datatype,
+        MPI_T_enum *enumtype, char *desc, int *desc_len, int *binding, int *readonly,
+        int *continuous, int *atomic) {
     REQUIRE_INIT();
     if (i < 0 || i >= (int)pvars().size()) return MPI_T_ERR_INVALID_INDEX;
     const PvarRef &r = pvars()[(size_t)i];
@@ -279,7 +279,7 @@ int PMPI_T_pvar_get_info(int i, char *name, int *name_len, int *verbosity, int *
     if (atomic) *atomic = 0;
     return MPI_SUCCESS;
 }
-int PMPI_T_pvar_get_index(const char *name, int var_class, int *index) {
+MPI_API(T_pvar_get_index, const char *name, int var_class, int *index) {
     REQUIRE_INIT();
     if (!name || !index) return MPI_ERR_ARG;
     for (int i = 0; i < (int)pvars().size(); ++i) {
@@ -291,13 +291,13 @@ int PMPI_T_pvar_get_index(const char *name, int var_class, int *index) {
     }
     return MPI_T_ERR_INVALID_NAME;
 }
-int PMPI_T_pvar_session_create(MPI_T_pvar_session *session) {
+MPI_API(T_pvar_session_create, MPI_T_pvar_session *session) {
     REQUIRE_INIT();
     if (!session) return MPI_ERR_ARG;
     *session = new MPIR_T_pvar_session_s();
     return MPI_SUCCESS;
 }
-int PMPI_T_pvar_session_free(MPI_T_pvar_session *session) {
+MPI_API(T_pvar_session_free, MPI_T_pvar_session *session) {
     REQUIRE_INIT();
     if (!session || !*session) return MPI_T_ERR_INVALID_SESSION;
     for (auto *h : (*session)->handles) delete h;
@@ -305,7 +305,7 @@ int PMPI_T_pvar_session_free(MPI_T_pvar_session *session) {
     *session = MPI_T_PVAR_SESSION_NULL;
     return MPI_SUCCESS;
 }
-int PMPI_T_pvar_handle_alloc(MPI_T_pvar_session session, int i, void *, MPI_T_pvar_handle *handle, int *count) {
+MPI_API(T_pvar_handle_alloc, MPI_T_pvar_session session, int i, void *, MPI_T_pvar_handle *handle, int *count) {
     REQUIRE_INIT();
     if (!session) return MPI_T_ERR_INVALID_SESSION;
     if (i < 0 || i >= (int)pvars().size()) return MPI_T_ERR_INVALID_INDEX;
@@ -316,7 +316,7 @@ int PMPI_T_pvar_handle_alloc(MPI_T_pvar_session session, int i, void *, MPI_T_pv
     *count = 1;
     return MPI_SUCCESS;
 }
-int PMPI_T_pvar_handle_free(MPI_T_pvar_session session, MPI_T_pvar_handle *handle) {
+MPI_API(T_pvar_handle_free, MPI_T_pvar_session session, MPI_T_pvar_handle *handle) {
     REQUIRE_INIT();
     if (!session) return MPI_T_ERR_INVALID_SESSION;
     if (!handle || !*handle || *handle == MPI_T_PVAR_ALL_HANDLES || (*handle)->session != session)
@@ -342,7 +342,7 @@ static int each_handle(MPI_T_pvar_session session, MPI_T_pvar_handle handle, voi
     fn(handle);
     return MPI_SUCCESS;
 }
-int PMPI_T_pvar_start(MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
+MPI_API(T_pvar_start, MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
     REQUIRE_INIT();
     return each_handle(session, handle, [](MPIR_T_pvar_handle_s *h) {
         if (h->started) return;
@@ -350,7 +350,7 @@ int PMPI_T_pvar_start(MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
         h->started = true;
     });
 }
-int PMPI_T_pvar_stop(MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
+MPI_API(T_pvar_stop, MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
     REQUIRE_INIT();
     return each_handle(session, handle, [](MPIR_T_pvar_handle_s *h) {
         if (!h->started) return;
@@ -358,7 +358,7 @@ int PMPI_T_pvar_stop(MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
         h->started = false;
     });
 }
-int PMPI_T_pvar_read(MPI_T_pvar_session session, MPI_T_pvar_handle handle, void *buf) {
+MPI_API(T_pvar_read, MPI_T_pvar_session session, MPI_T_pvar_handle handle, void *buf) {
     REQUIRE_INIT();
     if (!session) return MPI_T_ERR_INVALID_SESSION;
     if (handle == MPI_T_PVAR_ALL_HANDLES || !handle || handle->session != session) return MPI_T_ERR_INVALID_HANDLE;
@@ -373,28 +373,28 @@ int PMPI_T_pvar_read(MPI_T_pvar_session session, MPI_T_pvar_handle handle, void 
     return MPI_SUCCESS;
 }
 // READONLY variables (mv2_mpit.c registers them MPIR_T_PVAR_FLAG_READONLY)
-int PMPI_T_pvar_write(MPI_T_pvar_session session, MPI_T_pvar_handle handle, const void *) {
+MPI_API(T_pvar_write, MPI_T_pvar_session session, MPI_T_pvar_handle handle, const void *) {
     REQUIRE_INIT();
     if (!session) return MPI_T_ERR_INVALID_SESSION;
     if (!handle || (handle != MPI_T_PVAR_ALL_HANDLES && handle->session != session)) return MPI_T_ERR_INVALID_HANDLE;
     return MPI_T_ERR_PVAR_NO_WRITE;
 }
-int PMPI_T_pvar_reset(MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
+MPI_API(T_pvar_reset, MPI_T_pvar_session session, MPI_T_pvar_handle handle) {
     return PMPI_T_pvar_write(session, handle, nullptr);
 }
-int PMPI_T_pvar_readreset(MPI_T_pvar_session session, MPI_T_pvar_handle handle, void *) {
+MPI_API(T_pvar_readreset, MPI_T_pvar_session session, MPI_T_pvar_handle handle, void *) {
     return PMPI_T_pvar_write(session, handle, nullptr);
 }
 
 // ---- categories ----
-int PMPI_T_category_get_num(int *num) {
+MPI_API(T_category_get_num, int *num) {
     REQUIRE_INIT();
     if (!num) return MPI_ERR_ARG;
     *num = kNumCats;
     return MPI_SUCCESS;
 }
-int PMPI_T_category_get_info(int c, char *name, int *name_len, char *desc, int *desc_len, int *num_cvars,
-                             int *num_pvars, int *num_categories) {
+MPI_API(T_category_get_info, int c, char *name, int *name_len, char *desc, int *desc_len, int *num_cvars,
+        int *num_pvars, int *num_categories) {
     REQUIRE_INIT();
     if (c < 0 || c >= kNumCats) return MPI_T_ERR_INVALID_INDEX;
     put_str(kCats[c].name, name, name_len);
@@ -404,7 +404,7 @@ int PMPI_T_category_get_info(int c, char *name, int *name_len, char *desc, int *
     if (num_categories) *num_categories = 0;
     return MPI_SUCCESS;
 }
-int PMPI_T_category_get_index(const char *name, int *index) {
+MPI_API(T_category_get_index, const char *name, int *index) {
     REQUIRE_INIT();
     if (!name || !index) return MPI_ERR_ARG;
     for (int c = 0; c < kNumCats; ++c)
@@ -414,66 +414,30 @@ int PMPI_T_category_get_index(const char *name, int *index) {
         }
     return MPI_T_ERR_INVALID_NAME;
 }
-int PMPI_T_category_get_cvars(int c, int len, int indices[]) {
+MPI_API(T_category_get_cvars, int c, int len, int indices[]) {
     REQUIRE_INIT();
     if (c < 0 || c >= kNumCats) return MPI_T_ERR_INVALID_INDEX;
     if (c == kNumCats - 1)
         for (int i = 0; i < len && i < kNumCvars; ++i) indices[i] = i;
     return MPI_SUCCESS;
 }
-int PMPI_T_category_get_pvars(int c, int len, int indices[]) {
+MPI_API(T_category_get_pvars, int c, int len, int indices[]) {
     REQUIRE_INIT();
     if (c < 0 || c >= kNumCats) return MPI_T_ERR_INVALID_INDEX;
     const std::vector<int> v = cat_pvars(c);
     for (int i = 0; i < len && i < (int)v.size(); ++i) indices[i] = v[(size_t)i];
     return MPI_SUCCESS;
 }
-int PMPI_T_category_get_categories(int c, int, int *) {
+MPI_API(T_category_get_categories, int c, int, int *) {
     REQUIRE_INIT();
     if (c < 0 || c >= kNumCats) return MPI_T_ERR_INVALID_INDEX;
     return MPI_SUCCESS;
 }
-int PMPI_T_category_changed(int *stamp) {
+MPI_API(T_category_changed, int *stamp) {
     REQUIRE_INIT();
     if (!stamp) return MPI_ERR_ARG;
     *stamp = 0;  // the variable set is static
     return MPI_SUCCESS;
 }
-
-int MPI_T_init_thread(int required, int *provided) WEAK(MPI_T_init_thread);
-int MPI_T_finalize(void) WEAK(MPI_T_finalize);
-int MPI_T_enum_get_info(MPI_T_enum e, int *num, char *name, int *len) WEAK(MPI_T_enum_get_info);
-int MPI_T_enum_get_item(MPI_T_enum e, int i, int *v, char *name, int *len) WEAK(MPI_T_enum_get_item);
-int MPI_T_cvar_get_num(int *num) WEAK(MPI_T_cvar_get_num);
-int MPI_T_cvar_get_info(int i, char *name, int *nl, int *verb, MPI_Datatype *dt, MPI_T_enum *e, char *desc, int *dl,
-                        int *bind, int *scope) WEAK(MPI_T_cvar_get_info);
-int MPI_T_cvar_get_index(const char *name, int *i) WEAK(MPI_T_cvar_get_index);
-int MPI_T_cvar_handle_alloc(int i, void *obj, MPI_T_cvar_handle *h, int *count) WEAK(MPI_T_cvar_handle_alloc);
-int MPI_T_cvar_handle_free(MPI_T_cvar_handle *h) WEAK(MPI_T_cvar_handle_free);
-int MPI_T_cvar_read(MPI_T_cvar_handle h, void *buf) WEAK(MPI_T_cvar_read);
-int MPI_T_cvar_write(MPI_T_cvar_handle h, const void *buf) WEAK(MPI_T_cvar_write);
-int MPI_T_pvar_get_num(int *num) WEAK(MPI_T_pvar_get_num);
-int MPI_T_pvar_get_info(int i, char *name, int *nl, int *verb, int *cls, MPI_Datatype *dt, MPI_T_enum *e, char *desc,
-                        int *dl, int *bind, int *ro, int *cont, int *atomic) WEAK(MPI_T_pvar_get_info);
-int MPI_T_pvar_get_index(const char *name, int cls, int *i) WEAK(MPI_T_pvar_get_index);
-int MPI_T_pvar_session_create(MPI_T_pvar_session *s) WEAK(MPI_T_pvar_session_create);
-int MPI_T_pvar_session_free(MPI_T_pvar_session *s) WEAK(MPI_T_pvar_session_free);
-int MPI_T_pvar_handle_alloc(MPI_T_pvar_session s, int i, void *obj, MPI_T_pvar_handle *h, int *count)
-    WEAK(MPI_T_pvar_handle_alloc);
-int MPI_T_pvar_handle_free(MPI_T_pvar_session s, MPI_T_pvar_handle *h) WEAK(MPI_T_pvar_handle_free);
-int MPI_T_pvar_start(MPI_T_pvar_session s, MPI_T_pvar_handle h) WEAK(MPI_T_pvar_start);
-int MPI_T_pvar_stop(MPI_T_pvar_session s, MPI_T_pvar_handle h) WEAK(MPI_T_pvar_stop);
-int MPI_T_pvar_read(MPI_T_pvar_session s, MPI_T_pvar_handle h, void *buf) WEAK(MPI_T_pvar_read);
-int MPI_T_pvar_write(MPI_T_pvar_session s, MPI_T_pvar_handle h, const void *buf) WEAK(MPI_T_pvar_write);
-int MPI_T_pvar_reset(MPI_T_pvar_session s, MPI_T_pvar_handle h) WEAK(MPI_T_pvar_reset);
-int MPI_T_pvar_readreset(MPI_T_pvar_session s, MPI_T_pvar_handle h, void *buf) WEAK(MPI_T_pvar_readreset);
-int MPI_T_category_get_num(int *num) WEAK(MPI_T_category_get_num);
-int MPI_T_category_get_info(int c, char *name, int *nl, char *desc, int *dl, int *nc, int *np, int *ncat)
-    WEAK(MPI_T_category_get_info);
-int MPI_T_category_get_index(const char *name, int *c) WEAK(MPI_T_category_get_index);
-int MPI_T_category_get_cvars(int c, int len, int indices[]) WEAK(MPI_T_category_get_cvars);
-int MPI_T_category_get_pvars(int c, int len, int indices[]) WEAK(MPI_T_category_get_pvars);
-int MPI_T_category_get_categories(int c, int len, int indices[]) WEAK(MPI_T_category_get_categories);
-int MPI_T_category_changed(int *stamp) WEAK(MPI_T_category_changed);
 
 }  // extern "C"

@@ -463,6 +463,182 @@ def arg_checks(L, rank, n):
     return np.array([v for c in calls for v in c] + [bad], dtype=np.int64)
 
 
+def arg_order(L, rank, n, labels_path):
+    """The order of the argument checks of every MPI entry point, beside arg_checks' buffer tests:
+    each call below breaks one rule, or two so that the class returned names the check that comes
+    first.  Every call is refused on every rank that makes it, by a local check before any
+    collective of the runtime; where a check applies at the root only, the other ranks make
+    another refused call with an expectation of their own.  No invalid pointer but NULL and
+    MPI_IN_PLACE is passed.  Then one valid MPI_Allreduce proves no rank was left inside a
+    collective.  Returns [got, want] pairs per call and the valid call's wrong elements last; the
+    calls' names go to labels_path."""
+    I, F, LD = TYPES["MPI_INT"][0], TYPES["MPI_FLOAT"][0], TYPES["MPI_LONG_DOUBLE"][0]
+    SUM, BAND = OPS["MPI_SUM"], OPS["MPI_BAND"]
+    P, ci = ctypes.c_void_p, ctypes.c_int
+    IN_PLACE, NULL = P(-1 & 0xFFFFFFFFFFFFFFFF), P(0)
+    BUF, COUNT, TYPE, TAG, COMM, RANK, ROOT, OP, ARG, TRUNC, REQUEST, UNSUP = 1, 2, 3, 4, 5, 6, 7, 9, 12, 14, 19, 44
+    SELF, BADCOMM, BADT, BADOP, REQ_NULL, SENT = 0x44000001, 0x1234, 0x1234, 0x1234, 0x2C000000, -7
+    x = np.arange(4 * n, dtype=np.int32) + 10 * rank
+    a, b = m.DeviceBuffer.from_array(x), m.DeviceBuffer(16 * n)
+    A, B = P(a.ptr), P(b.ptr)
+    vt, vu, uop = ci(), ci(), ci()
+    assert L.MPI_Type_vector(2, 1, 2, I, ctypes.byref(vt)) == 0 and L.MPI_Type_commit(ctypes.byref(vt)) == 0
+    assert L.MPI_Type_vector(2, 1, 2, I, ctypes.byref(vu)) == 0  # never committed
+    VT, VU = vt.value, vu.value
+    FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ci), ctypes.POINTER(ci))
+    cb = FN(lambda inp, io, ln, dt: None)  # never called: every call that names it is refused
+    assert L.MPI_Op_create(ctypes.cast(cb, ctypes.c_void_p), 1, ctypes.byref(uop)) == 0
+    hip = ctypes.CDLL("libamdhip64.so")
+    st = ctypes.c_void_p()
+    assert hip.hipStreamCreate(ctypes.byref(st)) == 0
+
+    def arr(v):
+        return (ci * n)(*v)
+
+    ones, fours, idx, idx4 = arr([1] * n), arr([4] * n), arr(range(n)), arr(range(0, 4 * n, 4))
+    negc, negd = arr([1] * (n - 1) + [-1]), arr([-1] + list(range(1, n)))  # one negative count / displacement
+    types, badtypes = arr([I] * n), arr([I] * (n - 1) + [BADT])
+    root, me_root = 0, rank == 0
+    reqs = [ci(SENT) for _ in range(9)]
+    rq = [ctypes.byref(r) for r in reqs]
+    sum_op, rank_out = ci(SUM), ci(-1)
+    calls = [
+        # MPI_Reduce_local (reduce_local.c:206-237): count, op, type, then the buffers
+        ("Reduce_local count", L.MPI_Reduce_local(A, B, -1, I, SUM), COUNT),
+        ("Reduce_local op before type", L.MPI_Reduce_local(A, B, 4, BADT, BADOP), OP),
+        ("Reduce_local in place in", L.MPI_Reduce_local(IN_PLACE, B, 4, I, SUM), BUF),
+        ("Reduce_local in place inout", L.MPI_Reduce_local(A, IN_PLACE, 4, I, SUM), BUF),
+        ("Reduce_local alias count 0", L.MPI_Reduce_local(A, A, 0, I, SUM), 0),
+        # MPI_Allreduce (allreduce.c:863-899): communicator, count, type, op handle, committed, op on type
+        ("Allreduce count before type", L.MPI_Allreduce(A, B, -1, BADT, SUM, WORLD), COUNT),
+        ("Allreduce type before op", L.MPI_Allreduce(A, B, 4, BADT, BADOP, WORLD), TYPE),
+        ("Allreduce uncommitted", L.MPI_Allreduce(A, B, 1, VU, SUM, WORLD), TYPE),
+        ("Allreduce builtin op on derived", L.MPI_Allreduce(A, B, 1, VT, SUM, WORLD), OP),
+        ("Allreduce BAND on float", L.MPI_Allreduce(A, B, 4, F, BAND, WORLD), OP),
+        ("Allreduce comm", L.MPI_Allreduce(A, B, 4, I, SUM, BADCOMM), COMM),
+        # MPI_Reduce (reduce.c:1178): the root before the count
+        ("Reduce root n", L.MPI_Reduce(A, B, 4, I, SUM, n, WORLD), ROOT),
+        ("Reduce root before count", L.MPI_Reduce(A, B, -1, I, SUM, -1, WORLD), ROOT),
+        ("Reduce count", L.MPI_Reduce(A, B, -1, I, SUM, root, WORLD), COUNT),
+        ("Reduce op", L.MPI_Reduce(A, B, 4, I, BADOP, root, WORLD), OP),
+    ]
+    for name, scan in (("Scan", L.MPI_Scan), ("Exscan", L.MPI_Exscan)):  # scan.c:526-555, exscan.c:343-378
+        calls += [
+            (name + " alias", scan(A, A, 4, I, SUM, WORLD), BUF),
+            (name + " null send", scan(NULL, B, 4, I, SUM, WORLD), BUF),
+            (name + " op before alias", scan(A, A, 4, F, BAND, WORLD), OP),
+            (name + " count 0 null buffers", scan(NULL, NULL, 0, I, SUM, WORLD), 0),
+        ]
+    calls += [
+        # MPI_Reduce_scatter (red_scat.c:1168-1189): the counts first
+        ("Reduce_scatter count before type", L.MPI_Reduce_scatter(A, B, negc, BADT, SUM, WORLD), COUNT),
+        ("Reduce_scatter recv in place", L.MPI_Reduce_scatter(A, IN_PLACE, fours, I, SUM, WORLD), BUF),
+        # MPI_Allgather (allgather.c:952-987); the truncation is found before the runtime is entered
+        ("Allgather count", L.MPI_Allgather(A, 4, I, B, -1, I, WORLD), COUNT),
+        ("Allgather recvtype", L.MPI_Allgather(A, 4, I, B, 4, BADT, WORLD), TYPE),
+        ("Allgather truncate", L.MPI_Allgather(A, 4, I, B, 2, I, WORLD), TRUNC),
+        # MPI_Alltoall (alltoall.c:650-713)
+        ("Alltoall count", L.MPI_Alltoall(A, 4, I, B, -1, I, WORLD), COUNT),
+        ("Alltoall null recv", L.MPI_Alltoall(A, 4, I, NULL, 4, I, WORLD), BUF),
+        ("Alltoall recv in place", L.MPI_Alltoall(A, 4, I, IN_PLACE, 4, I, WORLD), BUF),
+        ("Alltoall alias", L.MPI_Alltoall(A, 4, I, A, 4, I, WORLD), BUF),
+        ("Alltoall truncate", L.MPI_Alltoall(A, 4, I, B, 2, I, WORLD), TRUNC),
+        # MPI_Alltoallv (alltoallv.c:520-594)
+        ("Alltoallv null recvcounts", L.MPI_Alltoallv(A, ones, idx, I, B, None, idx, I, WORLD), ARG),
+        ("Alltoallv count", L.MPI_Alltoallv(A, ones, idx, I, B, negc, idx, I, WORLD), COUNT),
+        ("Alltoallv uncommitted", L.MPI_Alltoallv(A, ones, idx, VU, B, ones, idx, I, WORLD), TYPE),
+        ("Alltoallv displacement", L.MPI_Alltoallv(A, ones, idx, I, B, ones, negd, I, WORLD), ARG),
+        ("Alltoallv alias", L.MPI_Alltoallv(A, ones, idx, I, A, ones, idx, I, WORLD), BUF),
+        # MPI_Alltoallw (alltoallw.c:425-530)
+        ("Alltoallw null recvtypes", L.MPI_Alltoallw(A, ones, idx4, types, B, ones, idx4, None, WORLD), ARG),
+        ("Alltoallw count", L.MPI_Alltoallw(A, negc, idx4, types, B, ones, idx4, types, WORLD), COUNT),
+        ("Alltoallw type", L.MPI_Alltoallw(A, ones, idx4, badtypes, B, ones, idx4, types, WORLD), TYPE),
+        ("Alltoallw alias", L.MPI_Alltoallw(A, ones, idx4, types, A, ones, idx4, types, WORLD), BUF),
+        ("Alltoallw displacement", L.MPI_Alltoallw(A, ones, negd, types, B, ones, idx4, types, WORLD), ARG),
+        # MPI_Gather (gather.c:823-905)
+        ("Gather root n", L.MPI_Gather(A, 4, I, B, 4, I, n, WORLD), ROOT),
+        ("Gather sendcount", L.MPI_Gather(A, -1, I, B, 4, I, root, WORLD), COUNT),
+        ("Gather uncommitted", L.MPI_Gather(A, 1, VU, B, 4, I, root, WORLD), TYPE),
+        ("Gather both in place", L.MPI_Gather(IN_PLACE, 4, I, IN_PLACE, 4, I, root, WORLD), BUF),
+        # MPI_Gatherv (gatherv.c:300-400): the n-block side is the root's
+        ("Gatherv null recvcounts | sendcount",
+         L.MPI_Gatherv(A, 4, I, B, None, idx4, I, root, WORLD) if me_root else
+         L.MPI_Gatherv(A, -1, I, B, fours, idx4, I, root, WORLD), ARG if me_root else COUNT),
+        ("Gatherv recvcounts[j] | null send",
+         L.MPI_Gatherv(A, 1, I, B, negc, idx, I, root, WORLD) if me_root else
+         L.MPI_Gatherv(NULL, 4, I, B, fours, idx4, I, root, WORLD), COUNT if me_root else BUF),
+        ("Gatherv displacement | uncommitted",
+         L.MPI_Gatherv(A, 1, I, B, ones, negd, I, root, WORLD) if me_root else
+         L.MPI_Gatherv(A, 1, VU, B, ones, idx, I, root, WORLD), ARG if me_root else TYPE),
+        # MPI_Scatter (scatter.c:740-820)
+        ("Scatter root n", L.MPI_Scatter(A, 4, I, B, 4, I, n, WORLD), ROOT),
+        ("Scatter recvcount", L.MPI_Scatter(A, 4, I, B, -1, I, root, WORLD), COUNT),
+        ("Scatter uncommitted", L.MPI_Scatter(A, 4, I, B, 1, VU, root, WORLD), TYPE),
+        ("Scatter both in place", L.MPI_Scatter(IN_PLACE, 4, I, IN_PLACE, 4, I, root, WORLD), BUF),
+        # MPI_Scatterv (scatterv.c:240-330)
+        ("Scatterv null sendcounts | recvcount",
+         L.MPI_Scatterv(A, None, idx4, I, B, 4, I, root, WORLD) if me_root else
+         L.MPI_Scatterv(A, fours, idx4, I, B, -1, I, root, WORLD), ARG if me_root else COUNT),
+        ("Scatterv sendcounts[j] | null recv",
+         L.MPI_Scatterv(A, negc, idx, I, B, 1, I, root, WORLD) if me_root else
+         L.MPI_Scatterv(A, fours, idx4, I, NULL, 4, I, root, WORLD), COUNT if me_root else BUF),
+        ("Scatterv displacement | uncommitted",
+         L.MPI_Scatterv(A, ones, negd, I, B, 1, I, root, WORLD) if me_root else
+         L.MPI_Scatterv(A, ones, idx, I, B, 1, VU, root, WORLD), ARG if me_root else TYPE),
+        # MPI_Allgatherv (allgatherv.c:1090-1160)
+        ("Allgatherv null displs", L.MPI_Allgatherv(A, 1, I, B, ones, None, I, WORLD), ARG),
+        ("Allgatherv count", L.MPI_Allgatherv(A, 1, I, B, negc, idx, I, WORLD), COUNT),
+        ("Allgatherv own block", L.MPI_Allgatherv(P(a.ptr + 16 * rank), 4, I, A, fours, idx4, I, WORLD), BUF),
+        ("Allgatherv displacement", L.MPI_Allgatherv(A, 1, I, B, ones, negd, I, WORLD), ARG),
+        # MPI_Bcast (bcast.c:1560-1582): count, type, root, committed
+        ("Bcast count before type", L.MPI_Bcast(B, -1, BADT, root, WORLD), COUNT),
+        ("Bcast type before root", L.MPI_Bcast(B, 4, BADT, n, WORLD), TYPE),
+        ("Bcast root before committed", L.MPI_Bcast(B, 1, VU, n, WORLD), ROOT),
+        # the stream-ordered calls: where the stream is tested among the blocking call's checks
+        ("Allreduce_enqueue null stream", L.MPIX_Allreduce_enqueue(A, B, 4, I, SUM, WORLD, None), ARG),
+        ("Allreduce_enqueue alias before stream", L.MPIX_Allreduce_enqueue(A, A, 4, I, SUM, WORLD, None), BUF),
+        ("Allreduce_enqueue user op", L.MPIX_Allreduce_enqueue(A, B, 4, I, uop.value, WORLD, st), ARG),
+        ("Allreduce_enqueue long double", L.MPIX_Allreduce_enqueue(A, B, 1, LD, SUM, WORLD, st), TYPE),
+        ("Reduce_enqueue root before stream", L.MPIX_Reduce_enqueue(A, B, 4, I, SUM, n, WORLD, None), ROOT),
+        ("Reduce_scatter_enqueue null recvcounts", L.MPIX_Reduce_scatter_enqueue(A, B, None, I, SUM, WORLD, st), ARG),
+        ("Allgather_enqueue stream before alias",
+         L.MPIX_Allgather_enqueue(P(a.ptr + 16 * rank), 4, I, A, 4, I, WORLD, None), ARG),
+        ("Allgather_enqueue derived", L.MPIX_Allgather_enqueue(A, 1, VT, B, 1, VT, WORLD, st), TYPE),
+        ("Alltoall_enqueue count before stream", L.MPIX_Alltoall_enqueue(A, 4, I, B, -1, I, WORLD, None), COUNT),
+        ("Bcast_enqueue stream before count", L.MPIX_Bcast_enqueue(B, -1, I, root, WORLD, None), ARG),
+        # point-to-point and requests
+        ("Isend tag", L.MPI_Isend(A, 4, I, (rank + 1) % n, -1, WORLD, rq[0]), TAG),
+        ("Irecv tag", L.MPI_Irecv(B, 4, I, (rank + 1) % n, -5, WORLD, rq[1]), TAG),
+        ("Isend dest n", L.MPI_Isend(A, 4, I, n, 0, WORLD, rq[2]), RANK),
+        ("Isend on MPI_COMM_SELF", L.MPI_Isend(A, 4, I, 0, 0, SELF, rq[3]), UNSUP),
+        ("Isend null request", L.MPI_Isend(A, 4, I, (rank + 1) % n, 0, WORLD, None), ARG),
+        ("Wait bad handle", L.MPI_Wait(ctypes.byref(ci(0x1234)), None), REQUEST),
+        ("Wait MPI_REQUEST_NULL", L.MPI_Wait(ctypes.byref(ci(REQ_NULL)), None), 0),
+        # a refused nonblocking collective makes no request
+        ("Iscan alias", L.MPI_Iscan(A, A, 4, I, SUM, WORLD, rq[4]), BUF),
+        ("Ialltoall null recv", L.MPI_Ialltoall(A, 4, I, NULL, 4, I, WORLD, rq[5]), BUF),
+        ("Igather root n", L.MPI_Igather(A, 4, I, B, 4, I, n, WORLD, rq[6]), ROOT),
+        ("Ibcast count", L.MPI_Ibcast(B, -1, I, root, WORLD, rq[7]), COUNT),
+        ("Ireduce root n", L.MPI_Ireduce(A, B, 4, I, SUM, n, WORLD, rq[8]), ROOT),
+    ]
+    calls += [(f"request {i} keeps its sentinel", r.value, SENT) for i, r in enumerate(reqs)]
+    calls += [
+        ("Op_free of MPI_SUM", L.MPI_Op_free(ctypes.byref(sum_op)), OP),
+        ("Comm_rank comm", L.MPI_Comm_rank(BADCOMM, ctypes.byref(rank_out)), COMM),
+    ]
+    assert hip.hipStreamSynchronize(st) == 0
+    hip.hipStreamDestroy(st)
+    assert L.MPI_Op_free(ctypes.byref(uop)) == 0
+    for t in (vt, vu):
+        L.MPI_Type_free(ctypes.byref(t))
+    assert L.MPI_Allreduce(A, B, 4 * n, I, SUM, WORLD) == 0
+    want = sum(np.arange(4 * n, dtype=np.int32) + 10 * r for r in range(n))
+    bad = int(np.count_nonzero(b.download(np.int32, count=4 * n) != want))
+    with open(labels_path, "w") as f:
+        json.dump([c[0] for c in calls], f)
+    return np.array([v for c in calls for v in c[1:]] + [bad], dtype=np.int64)
+
+
 def soak(L, case, rank, n):
     """A long seeded sequence of small and mid-size calls back to back on the same buffers —
     blocking, nonblocking and stream-ordered collectives of every kind, one-shot and pipelined
@@ -964,6 +1140,8 @@ def main():
             res = derived_no_alloc(L, case, rank, n)
         elif k == "arg_checks":
             res = arg_checks(L, rank, n)
+        elif k == "arg_order":
+            res = arg_order(L, rank, n, os.path.join(out, f"{case['id']}_labels_r{rank}.json"))
         elif k == "soak":
             res = soak(L, case, rank, n)
         elif k == "staged":  # host and misaligned operands: the staging of the node collectives

@@ -163,7 +163,7 @@ def test_collectives_multiprocess(n, geom, tmp_path, golden):
                                ("allreduce_inplace", "MPI_FLOAT", "MPI_SUM", 524291)):
         cases.append({"id": f"rg{seed}", "kind": kind, "type": t, "op": op, "count": count, "seed": seed})
         seed += 1
-    # x87 long double: reduced on the host in 80-bit (mpi_api.cpp ld_uop) in the reference's order
+    # x87 long double: reduced on the host in 80-bit (api_reduce.cpp ld_uop) in the reference's order
     for kind, op, count in (("allreduce", "MPI_SUM", 100), ("allreduce", "MPI_SUM", 70001),
                             ("allreduce", "MPI_MAX", 1000), ("reduce", "MPI_SUM", 30001)):
         cases.append({"id": f"x8{seed}", "kind": kind, "type": "MPI_LONG_DOUBLE", "op": op, "count": count,
@@ -990,6 +990,25 @@ def test_argument_checks_follow_the_reference(n, tmp_path):
         got = res(case["id"], r)
         pairs, bad = got[:-1].reshape(-1, 2), got[-1]
         wrong = [(i, int(g), int(w)) for i, (g, w) in enumerate(pairs) if g != w]
+        assert not wrong, f"rank {r}: (call, got, want) {wrong}"
+        assert bad == 0, f"rank {r}: the valid MPI_Allreduce after the refused calls is wrong"
+
+
+@pytest.mark.parametrize("n", [1, 3])
+def test_argument_check_order_follows_the_reference(n, tmp_path):
+    """The order of the argument checks of the reductions, scans, all-to-alls, rooted calls,
+    MPI_Bcast, the stream-ordered calls and point-to-point (mp_gpu_worker.arg_order): each call
+    breaks one rule, or two so that the class names the check that comes first, and is refused on
+    every rank before any rank enters a collective; a refused MPI_I* call leaves its request
+    alone; one valid MPI_Allreduce afterwards completes with the right sums."""
+    case = {"id": "order", "kind": "arg_order"}
+    res = run_workers(n, [case], tmp_path)
+    for r in range(n):
+        got = res(case["id"], r)
+        labels = json.loads((tmp_path / "out" / f"order_labels_r{r}.json").read_text())
+        pairs, bad = got[:-1].reshape(-1, 2), got[-1]
+        assert len(labels) == len(pairs)
+        wrong = [(labels[i], int(g), int(w)) for i, (g, w) in enumerate(pairs) if g != w]
         assert not wrong, f"rank {r}: (call, got, want) {wrong}"
         assert bad == 0, f"rank {r}: the valid MPI_Allreduce after the refused calls is wrong"
 

@@ -111,7 +111,7 @@ def test_errors_are_mpi_classes():
 
 def test_x87_long_double_device_buffers():
     """MPI_LONG_DOUBLE has no gfx950 representation: device operands are staged through the
-    host and reduced there in 80-bit x87 (mpi_api.cpp ld_uop), not rejected."""
+    host and reduced there in 80-bit x87 (api_reduce.cpp ld_uop), not rejected."""
     L = m.lib()
     x = (np.arange(100, dtype=np.longdouble) / 3).astype(np.longdouble)
     y = np.full(100, np.longdouble(1) / 7, dtype=np.longdouble)

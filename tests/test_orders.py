@@ -277,7 +277,7 @@ def eval_progs_fn(xs, progs, blk, e0, e1, fn):
 
 @pytest.mark.parametrize("commute", [1, 0])
 def test_user_op_plans_match_reference_restatement(commute):
-    """The user-op host path evaluates these plans with the user function (mpi_api.cpp); here
+    """The user-op host path evaluates these plans with the user function (api_reduce.cpp); here
     with the non-associative fn(in, io) = 2 in + 3 io against tests/ref_user.py."""
     from tests import ref_user
     fn = lambda a, b: (a * 2 + b * 3).astype(np.int32)

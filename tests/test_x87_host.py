@@ -1,6 +1,6 @@
 """x87 80-bit long double types (MPI_LONG_DOUBLE, MPI_C_LONG_DOUBLE_COMPLEX,
 MPI_LONG_DOUBLE_INT): gfx950 has no 80-bit float, so the library reduces them
-on the host with its own loops (mpi_api.cpp ld_uop), like the reference's
+on the host with its own loops (api_reduce.cpp ld_uop), like the reference's
 (oputil.h:316-349, opmaxloc.c:65-87).  Host-buffer MPI_Reduce_local here is
 host logic only (no GPU call); the -m gpu tests run the same types through the
 collectives with device buffers."""
