@@ -267,7 +267,7 @@ int mv2h_reduce_scatter_table(int n, long nbytes);
  * uop(in = node b[i], inout = node a[i]); *root the result's node.  Returns the node count, or minus
  * the count needed when cap is too small. */
 int mv2h_rs_noncomm_expr(int n, int me, int pof2_equal, int *leaf, int *a, int *b, int cap, int *root);
-/* The message schedules the host evaluates for a user op above 8 ranks (mpi/user_coll.cpp BigEval),
+/* The message schedules the host evaluates for a user op above 8 ranks (mpi/host_sched.cpp BigEval),
  * run on n int32 operands of count elements each (ops: operand r at ops + r * count) with the fixed
  * function inout = 2 in + 3 inout; commute as the op's flag.  Writes rank me's (MPI_Reduce: the
  * root's) result to out: recursive doubling (allreduce_osu.c:455-600), pt2pt_rs (:852-1000),

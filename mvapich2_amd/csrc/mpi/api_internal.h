@@ -15,6 +15,7 @@
 #include "../../../include/mpi.h"
 #include "../../../include/mv2h.h"
 #include "../common.h"
+#include "../runtime/world.h"  // MV2_API_LOCAL: the front end's own state and helpers are not exported
 #include "datatype.h"
 
 // The two names of an entry point on one line, followed by the body of PMPI_<name>: MPI_<name> is
@@ -25,9 +26,6 @@
 #define MPIX_API(name, ...)                                                     \
     int MPIX_##name(__VA_ARGS__) __attribute__((weak, alias("PMPIX_" #name)));  \
     int PMPIX_##name(__VA_ARGS__)
-
-// the front end's own state and helpers: not exported from libmpi.so
-#define MV2_API_LOCAL __attribute__((visibility("hidden")))
 
 namespace mv2 {
 

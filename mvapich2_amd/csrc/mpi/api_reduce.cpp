@@ -14,7 +14,7 @@ using namespace mv2;
 
 // ---- user-op path: user functions are host callbacks (the reference also
 // calls them on host copies of device buffers, reduce_local.c:54-164); the
-// collectives' host evaluation is user_coll.cpp ----
+// collectives' host evaluation is user_coll.cpp and its layers ----
 static int copy_to_host(HostBuf &h, const void *p, size_t bytes) {
     h.resize(bytes ? bytes : 1);
     if (!h.data()) return MPI_ERR_NO_MEM;

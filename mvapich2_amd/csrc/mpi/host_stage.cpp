@@ -1,0 +1,304 @@
+// host_stage.cpp — the staging layer of the host-evaluated reductions (user_coll.cpp has the
+// design): pinned host and device scratch, packed operands moved between the ranks, slices fetched
+// to the host in the type's layout, the programs run over them, results returned and collected.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../../include/mv2h.h"
+#include "user_coll_internal.h"
+
+namespace mv2 {
+
+void HostBuf::resize(size_t n) {
+    static char *buf[HS_COUNT];
+    static size_t cap[HS_COUNT];
+    static bool pinned[HS_COUNT];
+    if (n > cap[slot_]) {
+        if (buf[slot_]) {
+            if (pinned[slot_]) (void)hipHostFree(buf[slot_]);
+            else free(buf[slot_]);
+        }
+        const size_t want = std::max(n, 2 * cap[slot_]);
+        void *q = nullptr;
+        pinned[slot_] = hipHostMalloc(&q, want, hipHostMallocDefault) == hipSuccess;
+        if (!pinned[slot_]) {
+            (void)hipGetLastError();
+            q = malloc(want);  // no GPU (host-buffer x87 calls): plain memory
+        }
+        buf[slot_] = (char *)q;
+        cap[slot_] = q ? want : 0;
+    }
+    p_ = buf[slot_];
+    n_ = n;
+}
+
+char *dev_scratch(int slot, size_t bytes) {
+    static void *p[DS_COUNT];
+    static size_t cap[DS_COUNT];
+    if (bytes == 0) bytes = 1;
+    if (bytes > cap[slot]) {
+        // an abandoned collective receive may still be arriving into the old block (DS_ALL /
+        // DS_RES_ALL are receive areas): then it is left allocated rather than freed under it
+        if (p[slot] && !coll_context_poisoned()) mv2h_free(p[slot]);
+        p[slot] = nullptr;
+        cap[slot] = 0;
+        ++world().call_allocs;
+        if (mv2h_malloc(&p[slot], bytes)) return (char *)(p[slot] = nullptr);
+        cap[slot] = bytes;
+    }
+    return (char *)p[slot];
+}
+
+Job job() {
+    const World &w = world();
+    return w.nnodes > 1 ? Job{w.gsize, w.grank, true} : Job{w.size, w.rank, false};
+}
+
+Typed typed(MPI_Datatype dt) {
+    Typed t{dt, dtype_size(dt), dtype_extent(dt), false};
+    t.contig = dtype_is_contiguous(dt) && t.tsize == t.extent;
+    return t;
+}
+
+namespace {
+
+constexpr int kTagRanges = kCollTagBase - 4;  // the library's collective context (runtime/world.h)
+
+// n operands of `count` elements received `stride` bytes apart at all, elements [lo, hi) of each;
+// the call's counters of received operand bytes and of the receive area follow
+Operands received(const Typed &t, int n, int count, const char *all, size_t stride, long lo, long hi) {
+    world().uop_in_bytes = stride * (size_t)(n - 1);
+    world().uop_area_bytes = stride * (size_t)n;
+    return Operands{t, n, (size_t)count * (size_t)t.tsize, all, stride, lo, hi};
+}
+
+// every rank's whole packed operand on every rank (the device allgather)
+int gather_whole(const char *mine, int count, const Typed &t, int slot, Operands &o) {
+    const int n = job().n;
+    const size_t P = (size_t)count * (size_t)t.tsize;
+    char *all = dev_scratch(slot, P * (size_t)n);
+    if (!all) return MPI_ERR_NO_MEM;
+    o = received(t, n, count, all, P, 0, count);
+    if (n == 1) return mv2h_memcpy_dtod(all, mine, P) ? MPI_ERR_OTHER : 0;
+    return mv2h_allgather(mine, all, P, nullptr);
+}
+
+// the point-to-point channels reach every rank of the job (every node's ranks up to the rank mesh)
+bool channels_reach_all() {
+    const World &w = world();
+    return w.nnodes == 1 || w.gsize <= kMeshMaxRanks;
+}
+
+// one program's steps over cnt elements of the operands at W
+void run_steps(const Prog &p, char *W, long rspan, int cnt, const Typed &t, MPI_User_function *fn) {
+    for (int s = 0; s < p.nsteps; ++s)
+        call_uop(fn, W + (size_t)p.src[s] * rspan, W + (size_t)p.dst[s] * rspan, cnt, t.dt);
+}
+
+}  // namespace
+
+// this rank's operand packed on the device (DS_MINE)
+int pack_mine(const void *src, int count, const Typed &t, char **out) {
+    const size_t P = (size_t)count * (size_t)t.tsize;
+    char *mine = dev_scratch(DS_MINE, P);
+    if (!mine) return MPI_ERR_NO_MEM;
+    int rc;
+    if (mv2h_is_device_ptr(src)) {
+        rc = dtype_pack(src, count, t.dt, mine);
+    } else {
+        HostBuf h(HS_PACKED);
+        if (!h.reserve(P + 1)) return MPI_ERR_NO_MEM;
+        rc = dtype_pack(src, count, t.dt, h.data());
+        if (!rc && mv2h_memcpy_htod(mine, h.data(), P)) rc = MPI_ERR_OTHER;
+    }
+    *out = mine;
+    return rc;
+}
+
+// Rank j evaluates elements [bd[j], bd[j + 1]): this rank's range of every rank's packed operand
+// onto this rank (rank j's at all + j * stride), an all-to-all of ranges over the point-to-point
+// channels, each rank sent only the range it evaluates.  Beyond the channels' reach: the whole
+// operands, windowed.
+int exchange_ranges(const char *mine, int count, const Typed &t, const std::vector<long> &bd, Operands &o) {
+    const auto [n, me, multi] = job();
+    if (!channels_reach_all()) {
+        const int rc = gather_whole(mine, count, t, DS_ALL, o);
+        if (rc) return rc;
+        o.all += (size_t)bd[me] * (size_t)t.tsize;
+        o.lo = bd[me];
+        o.hi = bd[me + 1];
+        return 0;
+    }
+    const size_t ts = (size_t)t.tsize, mb = (size_t)(bd[me + 1] - bd[me]) * ts;
+    char *all = dev_scratch(DS_ALL, mb * (size_t)n);
+    if (!all) return MPI_ERR_NO_MEM;
+    o = received(t, n, count, all, mb, bd[me], bd[me + 1]);
+    std::vector<unsigned long long> reqs;
+    reqs.reserve(2 * (size_t)n);
+    int rc = 0;
+    for (int j = 0; j < n && !rc; ++j) {
+        if (j == me || !mb) continue;
+        unsigned long long q = 0;
+        if (!(rc = p2p_irecv(all + (size_t)j * mb, mb, j, kTagRanges, &q))) reqs.push_back(q);
+    }
+    for (int j = 0; j < n && !rc; ++j) {
+        const size_t jb = (size_t)(bd[j + 1] - bd[j]) * ts;
+        if (j == me || !jb) continue;
+        unsigned long long q = 0;
+        if (!(rc = p2p_isend(mine + (size_t)bd[j] * ts, jb, j, kTagRanges, &q))) reqs.push_back(q);
+    }
+    if (!rc && mb && mv2h_memcpy_dtod(all + (size_t)me * mb, mine + (size_t)bd[me] * ts, mb)) rc = MPI_ERR_OTHER;
+    return p2p_wait_all(reqs.data(), reqs.size(), rc) ? MPI_ERR_OTHER : 0;
+}
+
+// the whole packed operands on every rank (every element evaluated by every rank)
+int stage_operands(const void *src, int count, const Typed &t, Operands &o) {
+    char *mine = nullptr;
+    const int rc = pack_mine(src, count, t, &mine);
+    return rc ? rc : gather_whole(mine, count, t, DS_ALL, o);
+}
+
+// The operands a split needs, staged: the uniform part [0, U) by ranges (rank r gets range r of
+// every operand, ou), the own part [U, count) whole on every rank (oo; an allgather of those
+// elements only).  U = 0: every rank's whole operand (recursive doubling: each rank's own tree).
+int stage_split(const void *src, int count, const Typed &t, const Split &sp, Operands &ou, Operands &oo) {
+    char *mine = nullptr;
+    int rc = pack_mine(src, count, t, &mine);
+    if (rc) return rc;
+    if (sp.U == 0) return gather_whole(mine, count, t, DS_ALL, oo);
+    const int n = job().n;
+    const SplitRanges sr(sp.U, n);
+    std::vector<long> bd((size_t)n + 1);
+    for (int j = 0; j <= n; ++j) bd[j] = sr.lo(j);  // hi(j) = lo(j + 1)
+    if ((rc = exchange_ranges(mine, count, t, bd, ou))) return rc;
+    if (sp.U < count) {  // the own part: those elements of every operand
+        const size_t rb = (size_t)(count - sp.U) * (size_t)t.tsize;
+        char *rem = dev_scratch(DS_REM, rb * (size_t)n);
+        if (!rem) return MPI_ERR_NO_MEM;
+        if ((rc = mv2h_allgather(mine + (size_t)sp.U * (size_t)t.tsize, rem, rb, nullptr))) return rc;
+        oo = Operands{t, n, (size_t)count * (size_t)t.tsize, rem, rb, sp.U, count};  // the ranges' counters stand
+    }
+    return 0;
+}
+
+// Every rank's range of results (packed; range j of sr) into res_all at j * chunk: allgathered
+// (root < 0), or gathered at the root over the point-to-point channels (MPI_Reduce: only the
+// root's result counts)
+int collect_results(const char *res_mine, char *res_all, const SplitRanges &sr, size_t tsize, int root) {
+    const auto [n, me, multi] = job();
+    const size_t cb = (size_t)sr.chunk * tsize;
+    if (root < 0 || !channels_reach_all()) return mv2h_allgather(res_mine, res_all, cb, nullptr);
+    auto bytes_of = [&](int j) { return (size_t)(sr.hi(j) - sr.lo(j)) * tsize; };
+    int rc = 0;
+    unsigned long long q = 0;
+    std::vector<unsigned long long> reqs;
+    if (me != root) {  // this rank's range to the root
+        if (bytes_of(me) && !(rc = p2p_isend(res_mine, bytes_of(me), root, kTagRanges, &q))) reqs.push_back(q);
+        return p2p_wait_all(reqs.data(), reqs.size(), rc) ? MPI_ERR_OTHER : 0;
+    }
+    for (int j = 0; j < n && !rc; ++j) {
+        if (j == me || !bytes_of(j)) continue;
+        if (!(rc = p2p_irecv(res_all + (size_t)j * cb, bytes_of(j), j, kTagRanges, &q))) reqs.push_back(q);
+    }
+    if (!rc && bytes_of(me) && mv2h_memcpy_dtod(res_all + (size_t)me * cb, res_mine, bytes_of(me))) rc = MPI_ERR_OTHER;
+    return p2p_wait_all(reqs.data(), reqs.size(), rc) ? MPI_ERR_OTHER : 0;
+}
+
+// Elements [b, e) of every rank's operand in the type's layout (element b at offset 0),
+// operand j at W + j * rspan
+int fetch(const Operands &o, long b, long e, HostBuf &W, long &rspan) {
+    const Typed &t = o.t;
+    const int cnt = (int)(e - b);
+    if (b < o.lo || e > o.hi) return MPI_ERR_INTERN;  // outside what this rank received
+    rspan = dtype_span(t.dt, cnt);
+    const size_t rb = (size_t)cnt * (size_t)t.tsize;
+    if (!W.reserve((size_t)rspan * (size_t)o.n + 1)) return MPI_ERR_NO_MEM;
+    if (!cnt) return 0;
+    const char *src = o.all + (size_t)(b - o.lo) * (size_t)t.tsize;
+    if (t.contig)  // the slices land in place: one strided copy
+        return hipMemcpy2D(W.data(), (size_t)rspan, src, o.stride, rb, (size_t)o.n, hipMemcpyDeviceToHost) == hipSuccess
+                   ? 0 : MPI_ERR_OTHER;
+    // a derived layout: unpacked on the device (one kernel per operand), then one copy of the
+    // n spans — the host's own block loop over a sparse layout reads-for-ownership every line
+    // it half-writes, several times slower than moving the gaps over PCIe (r04r: 3.7 ms of a
+    // 4.4 ms call at 2 ranks)
+    if (char *sp = layout_on_device() ? dev_scratch(DS_SPAN, (size_t)rspan * (size_t)o.n) : nullptr) {
+        for (int j = 0; j < o.n; ++j) {
+            const int rc = dtype_unpack(src + (size_t)j * o.stride, cnt, t.dt, sp + (size_t)j * (size_t)rspan);
+            if (rc) return rc;
+        }
+        return mv2h_memcpy_dtoh(W.data(), sp, (size_t)rspan * (size_t)o.n) ? MPI_ERR_OTHER : 0;
+    }
+    HostBuf pk(HS_PACKED);
+    if (!pk.reserve(rb * (size_t)o.n + 1)) return MPI_ERR_NO_MEM;
+    if (hipMemcpy2D(pk.data(), rb, src, o.stride, rb, (size_t)o.n, hipMemcpyDeviceToHost) != hipSuccess)
+        return MPI_ERR_OTHER;
+    for (int j = 0; j < o.n; ++j) {
+        const int rc = dtype_unpack(pk.data() + (size_t)j * rb, cnt, t.dt, W.data() + (size_t)j * (size_t)rspan);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int eval_progs(const ProgSet &ps, long pbase, char *W, long rspan, long b, long e, const Typed &t,
+               MPI_User_function *fn, char *out, EvalSink sink) {
+    for (long x = b; x < e;) {
+        int k = 0;
+        long xe = e;
+        if (ps.nprog > 1) {
+            k = (int)std::min<long>((x - pbase) / (long)ps.blk, ps.nprog - 1);
+            if (k < ps.nprog - 1) xe = std::min<long>(e, pbase + (long)(k + 1) * (long)ps.blk);
+        }
+        const Prog &p = ps.p[k];
+        const size_t off = (size_t)(x - b) * (size_t)t.extent;
+        const int cnt = (int)(xe - x);
+        run_steps(p, W + off, rspan, cnt, t, fn);
+        const char *res = W + (size_t)p.res * rspan + off;
+        if (sink == SINK_LAYOUT) {
+            memcpy(out + off, res, (size_t)dtype_span(t.dt, cnt));
+        } else if (const int rc = dtype_pack(res, cnt, t.dt, out + (size_t)(x - b) * t.tsize)) {
+            return rc;
+        }
+        x = xe;
+    }
+    return 0;
+}
+
+// eval_progs with the packed result on the device at dev_out: a derived layout's result goes up
+// in the type's layout and is packed there (the host's pack loop is the slow part, see fetch)
+int eval_to_device(const ProgSet &ps, long pbase, char *W, long rspan, long b, long e, const Typed &t,
+                   MPI_User_function *fn, char *dev_out) {
+    const size_t pb = (size_t)(e - b) * (size_t)t.tsize;
+    if (e <= b) return 0;
+    int rc;
+    if (!t.contig && layout_on_device()) {
+        const long span = dtype_span(t.dt, (int)(e - b));
+        char *sp = dev_scratch(DS_SPAN, (size_t)span);
+        HostBuf R(HS_RESULT);
+        const char *up = nullptr;  // the result in the type's layout
+        if (sp && ps.nprog == 1) {  // one program: its steps in place, the result register goes up as it is
+            run_steps(ps.p[0], W, rspan, (int)(e - b), t, fn);
+            up = W + (size_t)ps.p[0].res * rspan;
+        } else if (R.reserve((size_t)span + 1) && sp) {
+            if ((rc = eval_progs(ps, pbase, W, rspan, b, e, t, fn, R.data(), SINK_LAYOUT))) return rc;
+            up = R.data();
+        }
+        if (up && mv2h_memcpy_htod(sp, up, (size_t)span)) return MPI_ERR_OTHER;
+        if (up) return dtype_pack(sp, (int)(e - b), t.dt, dev_out);
+    }
+    HostBuf R(HS_RESULT);
+    if (!R.reserve(pb + 1)) return MPI_ERR_NO_MEM;
+    if ((rc = eval_progs(ps, pbase, W, rspan, b, e, t, fn, R.data(), SINK_PACKED))) return rc;
+    return mv2h_memcpy_htod(dev_out, R.data(), pb) ? MPI_ERR_OTHER : 0;
+}
+
+// one rank: recvbuf's type map <- src's
+int copy_typemap(const void *src, void *recvbuf, int count, const Typed &t) {
+    char *tmp = dev_scratch(DS_MINE, (size_t)count * (size_t)t.tsize);
+    if (!tmp) return MPI_ERR_NO_MEM;
+    const int rc = dtype_pack(src, count, t.dt, tmp);
+    return rc ? rc : dtype_unpack(tmp, count, t.dt, recvbuf);
+}
+
+}  // namespace mv2

@@ -17,6 +17,7 @@ class HostBuf {
   public:
     explicit HostBuf(int slot) : slot_(slot) {}
     void resize(size_t n);
+    char *reserve(size_t n) { return resize(n), p_; }  // resized: the data, nullptr without memory
     char *data() { return p_; }
     const char *data() const { return p_; }
     size_t size() const { return n_; }

@@ -1,0 +1,137 @@
+// user_coll_internal.h — what the layers of the host-evaluated reductions share (user_coll.cpp's
+// header comment has the design): host_stage.cpp moves operands and results and runs programs,
+// host_sched.cpp evaluates message schedules beyond a program's size, rd_exchange.cpp is recursive
+// doubling by its messages, user_coll.cpp the four entry points.  Nothing here leaves libmpi.so.
+#pragma once
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "../runtime/orders.h"
+#include "../runtime/world.h"
+#include "datatype.h"
+#include "user_coll.h"
+
+namespace mv2 {
+
+// ---- host_stage.cpp ----
+// device scratch kept between calls, grown on demand
+enum DevSlot { DS_MINE, DS_ALL, DS_RES_MINE, DS_RES_ALL, DS_REM, DS_SPAN, DS_COUNT };
+MV2_API_LOCAL char *dev_scratch(int slot, size_t bytes);
+
+// the ranks a reduction runs over: the node's, or every rank of a job on several nodes
+struct Job {
+    int n, me;
+    bool multi;
+};
+MV2_API_LOCAL Job job();
+
+// Phase accounting of a host-evaluated call (World::uop_ns, mv2h_get_info "uop_*_us"): mark(p)
+// charges the time since the previous mark to phase p.
+enum UopPhase { UP_STAGE, UP_FETCH, UP_EVAL, UP_DELIVER };
+struct PhaseClock {
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void mark(int phase) {
+        const auto now = std::chrono::steady_clock::now();
+        world().uop_ns[phase] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(now - t).count();
+        t = now;
+    }
+};
+
+// Where a derived layout's gaps are handled: on the device (spans cross PCIe, gaps included) or
+// on the host (packed bytes cross PCIe, the host's block loop writes the spans).  A sparse span
+// costs the device route its gap bytes on the link, the host route a read-for-ownership pass over
+// the span; the link is the GPU's, shared by the ranks on it, the host loop is each rank's own
+// core.  Measured on the configs[4] vector (half gaps): the device route wins with the link to
+// itself or shared by 2 (4.4 -> 3.6 ms per call), the host route with 8 ranks on one link
+// (7.5 -> 10 ms); the crossover of the two costs is at a few ranks per link.
+inline bool layout_on_device() { return world().nshare <= 4; }
+
+struct Typed {
+    MPI_Datatype dt;
+    long tsize, extent;
+    bool contig;  // the packed layout is the type's layout
+};
+MV2_API_LOCAL Typed typed(MPI_Datatype dt);
+
+// one call of the user function: inout = in (op) inout over cnt elements of dt
+inline void call_uop(MPI_User_function *fn, const void *in, void *inout, int cnt, MPI_Datatype dt) {
+    fn((void *)in, inout, &cnt, &dt);
+}
+
+// every rank's operand, packed, on the device, for elements [lo, hi): rank j's element e at
+// all + j * stride + (e - lo) * tsize
+struct Operands {
+    Typed t;
+    int n;
+    size_t P;  // one whole packed operand
+    const char *all;
+    size_t stride;
+    long lo, hi;
+};
+
+// U elements split in n ranges of `chunk` elements, the last ones short or empty: range j is [lo(j), hi(j))
+struct SplitRanges {
+    long U, chunk;
+    SplitRanges(long U_, int n) : U(U_), chunk((U_ + n - 1) / n) {}
+    long lo(int j) const { return std::min<long>(U, (long)j * chunk); }
+    long hi(int j) const { return std::min<long>(U, lo(j) + chunk); }
+};
+
+// Elements [0, U) have the same programs on every rank (uni) and are split over the ranks;
+// [U, count) are this rank's own (own, program blocks counted from own_base)
+struct Split {
+    const ProgSet *uni;
+    long U;
+    const ProgSet *own;
+    long own_base;
+};
+
+MV2_API_LOCAL int pack_mine(const void *src, int count, const Typed &t, char **out);
+MV2_API_LOCAL int exchange_ranges(const char *mine, int count, const Typed &t, const std::vector<long> &bd,
+                                  Operands &o);
+MV2_API_LOCAL int stage_operands(const void *src, int count, const Typed &t, Operands &o);
+MV2_API_LOCAL int stage_split(const void *src, int count, const Typed &t, const Split &sp, Operands &ou, Operands &oo);
+MV2_API_LOCAL int collect_results(const char *res_mine, char *res_all, const SplitRanges &sr, size_t tsize, int root);
+MV2_API_LOCAL int fetch(const Operands &o, long b, long e, HostBuf &W, long &rspan);
+MV2_API_LOCAL int copy_typemap(const void *src, void *recvbuf, int count, const Typed &t);
+
+// Run ps over elements [b, e) held in W (element b at offset 0 of each operand, rspan bytes
+// apart); program blocks count from element `pbase`.  Step s is fn(in = w[src], inout = w[dst]).
+// The result goes to out, element b first: its type-map bytes packed, or in the type's layout.
+enum EvalSink { SINK_PACKED, SINK_LAYOUT };
+MV2_API_LOCAL int eval_progs(const ProgSet &ps, long pbase, char *W, long rspan, long b, long e, const Typed &t,
+                             MPI_User_function *fn, char *out, EvalSink sink);
+MV2_API_LOCAL int eval_to_device(const ProgSet &ps, long pbase, char *W, long rspan, long b, long e, const Typed &t,
+                                 MPI_User_function *fn, char *dev_out);
+
+// ---- host_sched.cpp ----
+// The fold of n ranks onto pof2 = 2^lev of them that the recursive algorithms start with
+// (allreduce_osu.c:455-505): of the first 2 * rem ranks every second one hands its operand to its
+// neighbour and takes the neighbour's result at the end; the others are renumbered 0 .. pof2 - 1
+struct Pof2Fold {
+    int pof2, lev, rem;
+    explicit Pof2Fold(int n) : pof2(floor_pof2(n)), lev(__builtin_ctz((unsigned)pof2)), rem(n - pof2) {}
+    // the newrank whose result rank r ends with
+    int newrank(int r) const { return r < 2 * rem ? r / 2 : r - rem; }
+    // the rank that runs as newrank q: the odd one of a folded pair, or the even one (redscat_gather)
+    int real(int q, bool even = false) const { return q < rem ? q * 2 + (even ? 0 : 1) : q + rem; }
+};
+
+// One rank's result of a message schedule (include/mv2h.h MV2H_SCHED_*) over the n operands at W (the
+// type's layout, rspan bytes apart, cnt elements each; left unchanged).  k: the knomial factor; for
+// MV2H_SCHED_RS_NONCOMM nonzero selects the mirror-permuted halving (equal blocks at a power of two).
+struct Sched {
+    int form, me, root, k;
+};
+// the result to out in the type's layout (rspan bytes), or its type-map bytes packed into R
+MV2_API_LOCAL int sched_eval(const Sched &s, const char *W, long rspan, int n, int cnt, const Typed &t,
+                             MPI_User_function *fn, bool comm, char *out);
+MV2_API_LOCAL int sched_eval_packed(const Sched &s, const char *W, long rspan, int n, int cnt, const Typed &t,
+                                    MPI_User_function *fn, bool comm, HostBuf &R);
+
+// ---- rd_exchange.cpp ----
+MV2_API_LOCAL int run_rd_exchange(const void *src, int count, const Typed &t, const HostOp &op, void *recvbuf,
+                                  bool *taken);
+
+}  // namespace mv2

@@ -27,12 +27,6 @@
 
 namespace mv2 {
 
-static int floor_pof2(int n) {
-    int p = 1;
-    while (p * 2 <= n) p *= 2;
-    return p;
-}
-
 // leaders: allgather of one section of `sect` bytes per node in the host buffer h (this node's at
 // h + node * sect), as a ring: step k passes node (node - k)'s section to the right
 static int leader_ring_sections(char *h, size_t sect) {
@@ -1028,8 +1022,9 @@ int mn_reduce_scatter(const void *sendbuf, void *recvbuf, const size_t *recvcoun
                ? 0 : E_INTERN;
 }
 
-// Host-evaluated reductions across nodes (user ops, x87 types; mpi/user_coll.cpp): the schedule the
-// device path above runs, as programs.  Allreduce: a non-commutative op fails every shortcut and
+// Host-evaluated reductions across nodes (user ops, x87 types; mpi/user_coll.cpp, a big schedule's
+// messages in mpi/host_sched.cpp): the schedule the device path above runs, as programs.
+// Allreduce: a non-commutative op fails every shortcut and
 // every two-level test and runs recursive doubling over the job (allreduce_osu.c:3359-3368);
 // MPI_Iallreduce the flat naive schedule; else mn_select's choice (flat ring wrapper / flat
 // pt2pt_rs or _rd / two-level with the entry's intra and inter functions).  Reduce: the flat

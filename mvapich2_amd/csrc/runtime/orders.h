@@ -20,6 +20,13 @@
 
 namespace mv2 {
 
+// the largest power of two not above n (n >= 1)
+static inline int floor_pof2(int n) {
+    int p = 1;
+    while (p * 2 <= n) p *= 2;
+    return p;
+}
+
 enum Algo : int {
     ALG_NONE = 0,            // one rank / REPLACE / NO_OP: no reduction order
     ALG_SHMEM_LINEAR = 1,    // reduce_shmem / MPIR_Reduce_shmem_MV2: ((x0 . x1) . x2) ...
@@ -165,7 +172,7 @@ int reduce_scatter_algo(int n, long nbytes);
 int plan_reduce_scatter(int n, int me, const size_t *counts, int tsize, int textent, Plan *out,
                         int opk = OPK_BUILTIN);
 // The expression of rank me's block of MPIR_Reduce_scatter_non_comm_MV2 over any number of ranks
-// (more than a program's registers: the host evaluates it, mpi/user_coll.cpp): pof2_equal selects
+// (more than a program's registers: the host evaluates it, mpi/host_sched.cpp): pof2_equal selects
 // MPIR_Reduce_scatter_noncomm_MV2's mirror-permuted halving (red_scat_osu.c:132-290), else the
 // recursive doubling (:1478-1722).  nodes[i].leaf >= 0: that rank's operand; else
 // uop(in = value of nodes[i].b, inout = value of nodes[i].a).  Returns the root node's index.
@@ -210,7 +217,7 @@ int nbc_kind();
 // node step's programs for local rank 0 over the node's ranks, `lead` = the leaders' programs over
 // the nodes' partials for the leader whose result this rank takes (its own node's, or for
 // MPI_Reduce the root's node).  big: more ranks (MN_FLAT) or nodes (MN_TWO_LEVEL's leaders) than
-// a program holds (kMaxRanks): the host evaluates the message schedule itself (mpi/user_coll.cpp):
+// a program holds (kMaxRanks): the host evaluates the message schedule itself (mpi/host_sched.cpp):
 // forced ALG_PT2PT_RD = recursive doubling, ALG_RING = the ring over [0, U) and recursive doubling
 // on the rest, ALG_BINOMIAL / ALG_KNOMIAL (factor k) / ALG_REDSCAT_GATHER = that reduce to `root` (a
 // node index for the leaders).

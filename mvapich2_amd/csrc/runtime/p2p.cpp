@@ -670,6 +670,17 @@ void mv2::p2p_abandon(unsigned long long id) {
     g_coll_poisoned = true;
 }
 
+int mv2::p2p_wait_all(const unsigned long long *reqs, size_t count, int rc) {
+    for (size_t i = 0; i < count; ++i) {
+        if (rc) {
+            p2p_abandon(reqs[i]);
+            continue;
+        }
+        if ((rc = mv2h_p2p_wait(reqs[i], nullptr, nullptr, nullptr))) p2p_abandon(reqs[i]);
+    }
+    return rc;
+}
+
 extern "C" {
 
 int mv2h_isend(const void *buf, size_t bytes, int dest, int tag, unsigned long long *req) {

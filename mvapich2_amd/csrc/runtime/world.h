@@ -24,6 +24,9 @@
 #include "../coll/kernels.h"
 #include "orders.h"
 
+// internal state and helpers shared between the library's files: not exported from libmpi.so
+#define MV2_API_LOCAL __attribute__((visibility("hidden")))
+
 namespace mv2 {
 
 constexpr int kShmMaxRanks = 64;
@@ -207,7 +210,7 @@ struct World {
     uint64_t done_queried = 0, done_late = 0, done_missed = 0, done_xcd_split = 0;
     uint64_t split_seen = 0;  // last done_flag[1] (split call's seq) already settled
     size_t uop_in_bytes = 0, uop_area_bytes = 0;  // last host-evaluated reduction: operand bytes received, area
-    // host-evaluated reductions, cumulative ns per phase (mpi/user_coll.cpp UopPhase): staging the
+    // host-evaluated reductions, cumulative ns per phase (mpi/user_coll_internal.h UopPhase): staging the
     // operands (device pack + exchange), fetching them to the host (D2H + unpack), evaluating (uop
     // calls + result pack), delivering (H2D + results' exchange + device unpack)
     uint64_t uop_ns[4] = {0, 0, 0, 0};
@@ -290,5 +293,8 @@ int p2p_irecv(void *buf, size_t cap, int source, int tag, unsigned long long *re
 // is still arriving (or a send still in flight) poisons the collective context, so every later
 // library collective fails instead of matching stale messages (runtime/p2p.cpp)
 void p2p_abandon(unsigned long long req);
+// waits for a collective's requests in order; once rc is set or a wait fails, every remaining
+// request is abandoned.  Returns rc, or the first failing wait's code
+MV2_API_LOCAL int p2p_wait_all(const unsigned long long *reqs, size_t count, int rc);
 
 }  // namespace mv2

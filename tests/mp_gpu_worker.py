@@ -882,6 +882,66 @@ def batch(L, case, rank, n):
     return np.concatenate(parts)
 
 
+def user_trace(L, case, rank, n, out):
+    """One host-evaluated reducing call (case["coll"]) whose user op, inout = 2 in + 3 inout on the
+    int32 type map, also records every call it receives: its *len, or -len - 1 where the datatype
+    handed to it is not the call's.  The operand is MPI_INT, or MPI_Type_vector(nblocks, 1, 2,
+    MPI_INT) with nblocks > 0; the receive buffer is prefilled with -7.  The trace goes to
+    <id>_trace_r<rank>.npy; returns the receive buffer's int32s, gaps included."""
+    nb, coll = case.get("nblocks", 0), case["coll"]
+    INT = TYPES["MPI_INT"][0]
+    per, ext_i = max(nb, 1), (nb - 1) * 2 + 1 if nb else 1
+    dt = ctypes.c_int(INT)
+    if nb:
+        assert L.MPI_Type_vector(nb, 1, 2, INT, ctypes.byref(dt)) == 0
+        assert L.MPI_Type_commit(ctypes.byref(dt)) == 0
+    FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                          ctypes.POINTER(ctypes.c_int))
+    trace = []
+
+    def uop(inp, io, ln, dtp):
+        c = ln[0]
+        trace.append(c if dtp[0] == dt.value else -c - 1)
+        if c <= 0:
+            return
+        shape, strides = (c, per), (ext_i * 4, 8)
+        a = np.lib.stride_tricks.as_strided(
+            np.ctypeslib.as_array((ctypes.c_int * (c * ext_i)).from_address(inp)), shape, strides)
+        b = np.lib.stride_tricks.as_strided(
+            np.ctypeslib.as_array((ctypes.c_int * (c * ext_i)).from_address(io)), shape, strides)
+        b[...] = a * 2 + b * 3
+    cb = FN(uop)
+    op = ctypes.c_int()
+    assert L.MPI_Op_create(ctypes.cast(cb, ctypes.c_void_p), case["commute"], ctypes.byref(op)) == 0
+    counts = case.get("recvcounts")
+    count = sum(counts) if counts else case["count"]
+    got = counts[rank] if counts else count
+    x = ((np.arange(count * ext_i) + rank) % 7).astype(np.int32)
+    sb = m.DeviceBuffer.from_array(x)
+    rb = m.DeviceBuffer.from_array(np.full(max(1, got * ext_i), -7, dtype=np.int32))
+    in_place = ctypes.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF)
+    if coll == "allreduce":
+        rc = L.MPI_Allreduce(sb.ptr, rb.ptr, count, dt.value, op.value, WORLD)
+    elif coll == "allreduce_inplace":
+        rc = L.MPI_Allreduce(in_place, sb.ptr, count, dt.value, op.value, WORLD)
+        rb = sb
+    elif coll == "reduce":
+        rc = L.MPI_Reduce(sb.ptr, rb.ptr, count, dt.value, op.value, case["root"], WORLD)
+    elif coll in ("scan", "exscan"):
+        rc = (L.MPI_Exscan if coll == "exscan" else L.MPI_Scan)(sb.ptr, rb.ptr, count, dt.value, op.value, WORLD)
+    elif coll == "reduce_scatter":
+        rc = L.MPI_Reduce_scatter(sb.ptr, rb.ptr, (ctypes.c_int * n)(*counts), dt.value, op.value, WORLD)
+    else:
+        raise ValueError(coll)
+    assert rc == 0, (case["id"], rc)
+    res = rb.download(np.int32, count=got * ext_i)
+    np.save(os.path.join(out, f"{case['id']}_trace_r{rank}.npy"), np.array(trace, dtype=np.int64))
+    L.MPI_Op_free(ctypes.byref(op))
+    if nb:
+        L.MPI_Type_free(ctypes.byref(dt))
+    return res
+
+
 def main():
     spec = json.load(open(sys.argv[1]))
     out = sys.argv[2]
@@ -1129,11 +1189,13 @@ def main():
             rc = L.MPI_Allreduce(sb.ptr, rb.ptr, cnt, vt.value, op.value, WORLD)
             assert rc == 0, (case["id"], rc)
             res = rb.download(np.uint8, count=cnt * ext_f * 4)
-            # the operand bytes this rank received, and its receive area (mpi/user_coll.cpp staging)
+            # the operand bytes this rank received, and its receive area (mpi/host_stage.cpp)
             np.save(os.path.join(out, f"{case['id']}_staged_r{rank}.npy"),
                     np.array([m.info("uop_in_bytes"), m.info("uop_area_bytes")], dtype=np.int64))
             L.MPI_Op_free(ctypes.byref(op))
             L.MPI_Type_free(ctypes.byref(vt))
+        elif k == "user_trace":  # a user op that records how the work is cut into calls
+            res = user_trace(L, case, rank, n, out)
         elif k.startswith("big_") or k in ("huge", "gib_allreduce"):
             res = big_case(L, case, rank, n)
         elif k == "derived_no_alloc":

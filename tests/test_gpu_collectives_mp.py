@@ -18,7 +18,7 @@ import pytest
 
 from mvapich2_amd.consts import DEVICE_UNSUPPORTED, OPS, TYPES
 from oracle import oracle
-from tests import ref_user
+from tests import ref_scan, ref_user
 from tests.helpers import as_bytes, assert_bytes_equal, rand_typed
 
 pytestmark = pytest.mark.gpu
@@ -462,7 +462,7 @@ def test_user_op_on_strided_vector_operand(n, xchg, tmp_path):
             ring = cnt * nb * 16 >= (2 << 20) and cnt >= n  # the ring wrapper (2 MiB and up, n <= 8)
             algo = oracle.ALGOS[oracle.allreduce_select(n, P, 0x4c00010d, False, 1)]  # MPI_BYTE sizing
             if (algo == "pt2pt_rd" or (algo == "ring_wrapper" and cnt < n)) and (n >= 4 or xchg == "1"):
-                # recursive doubling with its exchanges (user_coll.cpp run_rd_exchange, from 4
+                # recursive doubling with its exchanges (rd_exchange.cpp run_rd_exchange, from 4
                 # ranks on): one operand per step received, the pre- or post-step's included
                 pof2 = ref_user.pof2_of(n)
                 rem = n - pof2
@@ -475,6 +475,246 @@ def test_user_op_on_strided_vector_operand(n, xchg, tmp_path):
             else:  # smaller: a tree order (split by ranges) or recursive doubling (whole operands)
                 assert inb <= (n - 1) * P and (inb == (n - 1) * P or inb <= (n - 1) * -(-cnt // n) * nb * 16), \
                     (case["id"], r, inb, P)
+
+
+def trace_cases(n, rows=None):
+    """the calls of the user-op call-trace tests: (id, call, commutative, blocks of the vector type
+    or 0 for MPI_INT, count); Reduce goes to root 1, Reduce_scatter's blocks include an empty one"""
+    rows = rows or [("ar", "allreduce", 1, 0, 7), ("ari", "allreduce_inplace", 1, 0, 7), ("arn", "allreduce", 0, 0, 7),
+                    ("arv", "allreduce", 1, 3, 5), ("ariv", "allreduce_inplace", 1, 3, 5),
+                    # 7 x 16 KiB selects recursive doubling: every rank its own tree over whole operands
+                    # (the programs), or its exchanges (from 4 ranks on, or as MV2AMD_UOP_EXCHANGE says)
+                    ("rdv", "allreduce", 1, 4096, 7), ("rdiv", "allreduce_inplace", 1, 4096, 7),
+                    ("rdnv", "allreduce", 0, 4096, 7),
+                    # 11 x 256 KiB: the ring wrapper over 11 // n * n elements, the rest each rank's own;
+                    # in place: no ring, recursive doubling over all 11
+                    ("ring", "allreduce", 1, 65536, 11), ("ringi", "allreduce_inplace", 1, 65536, 11),
+                    ("rc", "reduce", 1, 0, 7), ("rn", "reduce", 0, 0, 7),
+                    ("sc", "scan", 1, 0, 7), ("scn", "scan", 0, 0, 7), ("ex", "exscan", 1, 0, 7), ("exn", "exscan", 0, 0, 7),
+                    ("rsc", "reduce_scatter", 1, 0, None), ("rsn", "reduce_scatter", 0, 0, None)]
+    cases = []
+    for cid, coll, commute, nb, count in rows:
+        case = {"id": cid, "kind": "user_trace", "coll": coll, "commute": commute, "nblocks": nb, "root": 1}
+        if coll == "reduce_scatter":
+            case["recvcounts"] = [2, 0, 3, 1, 2, 1, 0, 2][:n]
+        else:
+            case["count"] = count
+        cases.append(case)
+    return cases
+
+
+def check_trace_results(case, n, res, want):
+    """every rank's receive buffer of a user_trace case against want[r] (the type map's int32s; None:
+    never written); bytes outside the type map keep what they held"""
+    nb = case["nblocks"]
+    per, ext_i = max(nb, 1), (nb - 1) * 2 + 1 if nb else 1
+    for r in range(n):
+        got = res(case["id"], r)
+        c = len(got) // ext_i
+        held = np.full(len(got), -7, dtype=np.int32)
+        if case["coll"] == "allreduce_inplace":
+            held = ((np.arange(len(got)) + r) % 7).astype(np.int32)
+        if want[r] is not None:
+            np.lib.stride_tricks.as_strided(held, (c, per), (ext_i * 4, 8))[...] = np.asarray(want[r]).reshape(c, per)
+        assert np.array_equal(got, held), (case["id"], r, got[:16], held[:16])
+
+
+def trace_operands(case, n):
+    """every rank's operand of a user_trace case: (count, type-map ints per element)"""
+    nb = case["nblocks"]
+    per, ext_i = max(nb, 1), (nb - 1) * 2 + 1 if nb else 1
+    count = sum(case["recvcounts"]) if "recvcounts" in case else case["count"]
+    xs = []
+    for r in range(n):
+        x = ((np.arange(count * ext_i) + r) % 7).astype(np.int32)
+        xs.append(np.lib.stride_tricks.as_strided(x, (count, per), (ext_i * 4, 8)).copy())
+    return xs
+
+
+# Every rank's calls of the user function (*len of each, in order) as the library made them before
+# its host evaluation was split into layers: recorded once from that build, never derived.
+# {(ranks, MV2AMD_UOP_EXCHANGE): {case: [rank 0's calls, rank 1's, ...]}}
+TRACES = {
+    (2, None): {
+        'ar': [[4], [3]],
+        'ari': [[4], [3]],
+        'arn': [[4], [3]],
+        'arv': [[3], [2]],
+        'ariv': [[3], [2]],
+        'rdv': [[7], [7]],
+        'rdiv': [[7], [7]],
+        'rdnv': [[4], [3]],
+        'ring': [[5, 1], [5, 1]],
+        'ringi': [[11], [11]],
+        'rc': [[4], [3]],
+        'rn': [[4], [3]],
+        'sc': [[], [7]],
+        'scn': [[], [7]],
+        'ex': [[], []],
+        'exn': [[], []],
+        'rsc': [[2], []],
+        'rsn': [[2], []],
+    },
+    (3, None): {
+        'ar': [[3, 3], [3, 3], [1, 1]],
+        'ari': [[3, 3], [3, 3], [1, 1]],
+        'arn': [[3, 3], [3, 3], [1, 1]],
+        'arv': [[2, 2], [2, 2], [1, 1]],
+        'ariv': [[2, 2], [2, 2], [1, 1]],
+        'rdv': [[7, 7], [7, 7], [7, 7]],
+        'rdiv': [[7, 7], [7, 7], [7, 7]],
+        'rdnv': [[3, 3], [3, 3], [1, 1]],
+        'ring': [[3, 3, 2, 2], [3, 3, 2, 2], [3, 3, 2, 2]],
+        'ringi': [[11, 11], [11, 11], [11, 11]],
+        'rc': [[3, 3], [3, 3], [1, 1]],
+        'rn': [[3, 3], [3, 3], [1, 1]],
+        'sc': [[], [7], [7, 7]],
+        'scn': [[], [7], [7, 7]],
+        'ex': [[], [], [7]],
+        'exn': [[], [], [7]],
+        'rsc': [[2, 2], [], [3, 3]],
+        'rsn': [[2, 2], [], [3, 3]],
+    },
+    (5, None): {
+        'ar': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'ari': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'arn': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'arv': [[1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1]],
+        'ariv': [[1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1]],
+        'rdv': [[], [7, 7, 7], [7, 7], [7, 7], [7, 7]],
+        'rdiv': [[], [7, 7, 7], [7, 7], [7, 7], [7, 7]],
+        'rdnv': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'ring': [[2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1],
+                 [2, 2, 2, 2, 1, 1, 1, 1]],
+        'ringi': [[], [11, 11, 11], [11, 11], [11, 11], [11, 11]],
+        'rc': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'rn': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'sc': [[], [7], [7, 7], [7, 7, 7], [7, 7, 7, 7]],
+        'scn': [[], [7], [7, 7], [7, 7, 7], [7, 7, 7, 7]],
+        'ex': [[], [], [7], [7, 7], [7, 7, 7]],
+        'exn': [[], [], [7], [7, 7], [7, 7, 7]],
+        'rsc': [[2, 2, 2, 2], [], [3, 3, 3, 3], [1, 1, 1, 1], [2, 2, 2, 2]],
+        'rsn': [[2, 2, 2, 2], [], [3, 3, 3, 3], [1, 1, 1, 1], [2, 2, 2, 2]],
+    },
+    (5, '1'): {
+        'ar': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'ari': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'arn': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'arv': [[1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1]],
+        'ariv': [[1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1]],
+        'rdv': [[], [7, 7, 7], [7, 7], [7, 7], [7, 7]],
+        'rdiv': [[], [7, 7, 7], [7, 7], [7, 7], [7, 7]],
+        'rdnv': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'ring': [[2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1],
+                 [2, 2, 2, 2, 1, 1, 1, 1]],
+        'ringi': [[], [11, 11, 11], [11, 11], [11, 11], [11, 11]],
+        'rc': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'rn': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'sc': [[], [7], [7, 7], [7, 7, 7], [7, 7, 7, 7]],
+        'scn': [[], [7], [7, 7], [7, 7, 7], [7, 7, 7, 7]],
+        'ex': [[], [], [7], [7, 7], [7, 7, 7]],
+        'exn': [[], [], [7], [7, 7], [7, 7, 7]],
+        'rsc': [[2, 2, 2, 2], [], [3, 3, 3, 3], [1, 1, 1, 1], [2, 2, 2, 2]],
+        'rsn': [[2, 2, 2, 2], [], [3, 3, 3, 3], [1, 1, 1, 1], [2, 2, 2, 2]],
+    },
+    (3, '1'): {
+        'ar': [[3, 3], [3, 3], [1, 1]],
+        'ari': [[3, 3], [3, 3], [1, 1]],
+        'arn': [[3, 3], [3, 3], [1, 1]],
+        'arv': [[2, 2], [2, 2], [1, 1]],
+        'ariv': [[2, 2], [2, 2], [1, 1]],
+        'rdv': [[], [7, 7], [7]],
+        'rdiv': [[], [7, 7], [7]],
+        'rdnv': [[3, 3], [3, 3], [1, 1]],
+        'ring': [[3, 3, 2, 2], [3, 3, 2, 2], [3, 3, 2, 2]],
+        'ringi': [[], [11, 11], [11]],
+        'rc': [[3, 3], [3, 3], [1, 1]],
+        'rn': [[3, 3], [3, 3], [1, 1]],
+        'sc': [[], [7], [7, 7]],
+        'scn': [[], [7], [7, 7]],
+        'ex': [[], [], [7]],
+        'exn': [[], [], [7]],
+        'rsc': [[2, 2], [], [3, 3]],
+        'rsn': [[2, 2], [], [3, 3]],
+    },
+    (3, '0'): {
+        'ar': [[3, 3], [3, 3], [1, 1]],
+        'ari': [[3, 3], [3, 3], [1, 1]],
+        'arn': [[3, 3], [3, 3], [1, 1]],
+        'arv': [[2, 2], [2, 2], [1, 1]],
+        'ariv': [[2, 2], [2, 2], [1, 1]],
+        'rdv': [[7, 7], [7, 7], [7, 7]],
+        'rdiv': [[7, 7], [7, 7], [7, 7]],
+        'rdnv': [[3, 3], [3, 3], [1, 1]],
+        'ring': [[3, 3, 2, 2], [3, 3, 2, 2], [3, 3, 2, 2]],
+        'ringi': [[11, 11], [11, 11], [11, 11]],
+        'rc': [[3, 3], [3, 3], [1, 1]],
+        'rn': [[3, 3], [3, 3], [1, 1]],
+        'sc': [[], [7], [7, 7]],
+        'scn': [[], [7], [7, 7]],
+        'ex': [[], [], [7]],
+        'exn': [[], [], [7]],
+        'rsc': [[2, 2], [], [3, 3]],
+        'rsn': [[2, 2], [], [3, 3]],
+    },
+    (5, '0'): {
+        'ar': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'ari': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'arn': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'arv': [[1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1]],
+        'ariv': [[1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1]],
+        'rdv': [[7, 7, 7, 7], [7, 7, 7, 7], [7, 7, 7, 7], [7, 7, 7, 7], [7, 7, 7, 7]],
+        'rdiv': [[7, 7, 7, 7], [7, 7, 7, 7], [7, 7, 7, 7], [7, 7, 7, 7], [7, 7, 7, 7]],
+        'rdnv': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'ring': [[2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1], [2, 2, 2, 2, 1, 1, 1, 1],
+                 [2, 2, 2, 2, 1, 1, 1, 1]],
+        'ringi': [[11, 11, 11, 11], [11, 11, 11, 11], [11, 11, 11, 11], [11, 11, 11, 11], [11, 11, 11, 11]],
+        'rc': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'rn': [[2, 2, 2, 2], [2, 2, 2, 2], [2, 2, 2, 2], [1, 1, 1, 1], []],
+        'sc': [[], [7], [7, 7], [7, 7, 7], [7, 7, 7, 7]],
+        'scn': [[], [7], [7, 7], [7, 7, 7], [7, 7, 7, 7]],
+        'ex': [[], [], [7], [7, 7], [7, 7, 7]],
+        'exn': [[], [], [7], [7, 7], [7, 7, 7]],
+        'rsc': [[2, 2, 2, 2], [], [3, 3, 3, 3], [1, 1, 1, 1], [2, 2, 2, 2]],
+        'rsn': [[2, 2, 2, 2], [], [3, 3, 3, 3], [1, 1, 1, 1], [2, 2, 2, 2]],
+    },
+}
+
+
+@pytest.mark.timeout(200)
+@pytest.mark.parametrize("n,xchg", [(2, None), (3, None), (5, None), (5, "1"), (3, "1"), (3, "0"), (5, "0")])
+def test_user_op_call_trace_is_unchanged(n, xchg, tmp_path):
+    """How a host-evaluated reduction cuts its work into calls of the user function — the order of
+    the calls and each call's *len and datatype, per rank — is what a user op observes beyond the
+    result.  Allreduce (small sizes split by ranges, the ring with a remainder, MPI_IN_PLACE, a
+    derived type), Reduce, Scan / Exscan and Reduce_scatter at 2, 3 and 5 ranks.  The "rd" and
+    "ringi" rows are sized into recursive doubling: by its exchanges at 5 ranks and with
+    MV2AMD_UOP_EXCHANGE=1 (the pre-step's call, then one per doubling step, each of the whole
+    count; an even rank below 2 * rem makes none), by every rank's own program over the whole
+    operands below 4 ranks and with MV2AMD_UOP_EXCHANGE=0 (n - 1 calls of the whole count).  Every
+    rank's trace equals the recorded one exactly, and the results follow tests/ref_user.py /
+    ref_scan.py as in the tests above."""
+    cases = trace_cases(n)
+    res = run_workers(n, cases, tmp_path, extra_env={"MV2AMD_UOP_EXCHANGE": xchg} if xchg else None)
+    got = {case["id"]: [res(case["id"] + "_trace", r).tolist() for r in range(n)] for case in cases}
+    h = TYPES["MPI_INT"][0]
+    for case in cases:
+        coll, commute, nb = case["coll"], bool(case["commute"]), case["nblocks"]
+        xs = trace_operands(case, n)
+        if coll in ("allreduce", "allreduce_inplace"):
+            count = case["count"]
+            want = ref_user.allreduce(xs, ufn, commute, None if nb else h, count, in_place=coll == "allreduce_inplace",
+                                      nbytes=count * nb * 4 if nb else None)
+        elif coll == "reduce":
+            full = ref_user.reduce(xs, ufn, commute, h, case["count"], case["root"])
+            want = [full if r == case["root"] else None for r in range(n)]
+        elif coll in ("scan", "exscan"):
+            want = getattr(ref_scan, coll)(xs, ref_scan.user_fn_2a3b, commute=commute)
+        else:
+            want = user_reduce_scatter_expected(n, case["recvcounts"], commute)
+        check_trace_results(case, n, res, want)
+    for case in cases:
+        assert got[case["id"]] == TRACES[(n, xchg)][case["id"]], (case["id"], got[case["id"]])
 
 
 @pytest.mark.timeout(480)

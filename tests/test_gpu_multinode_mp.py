@@ -20,7 +20,7 @@ from mvapich2_amd.consts import OPS, TYPES
 from oracle import oracle
 from tests import ref_user
 from tests.helpers import as_bytes, assert_bytes_equal
-from tests.test_gpu_collectives_mp import inputs, run_workers
+from tests.test_gpu_collectives_mp import check_trace_results, inputs, run_workers, trace_cases, trace_operands
 
 pytestmark = pytest.mark.gpu
 
@@ -487,6 +487,21 @@ def user_reduce_across(xs, commute, count, ppn, root):
     return run(xs, "b" if inter == "r" else inter, root)
 
 
+def user_reduce_scatter_across(xs, commute, counts, ppn):
+    """MPI_Reduce_scatter with a user op across nodes, every rank's block: MPIR_Reduce_scatter_MV2's
+    flat selection, its basic algorithm the multi-node reduce to rank 0 + scatter"""
+    n, total = len(xs), sum(counts)
+    if commute and rs_algo(n, total * 4) == "rs_basic":
+        parts = [ref_user.reduce(xs[j * ppn:(j + 1) * ppn], _ufn, True, TYPES["MPI_INT"][0], total, 0)
+                 for j in range(n // ppn)] if ppn > 1 else xs
+        full = ref_user.binomial(parts, _ufn, 0, True)
+        offs = np.cumsum([0] + counts)
+        return [full[offs[r]:offs[r + 1]] for r in range(n)]
+    if commute:
+        return ref_user.reduce_scatter(xs, _ufn, TYPES["MPI_INT"][0], counts, algo=rs_algo(n, total * 4))
+    return ref_user.reduce_scatter_noncomm(xs, _ufn, counts)
+
+
 @pytest.mark.timeout(300)
 # (ranks, ranks per node, MV2AMD_MN_PROG_MAX): at most 8 processes share the one GPU (DESIGN.md §5
 # "Ranks per GPU"), so the schedules of jobs above 8 ranks / 8 nodes run at 8 and 6 ranks with the
@@ -499,7 +514,7 @@ def test_user_ops_across_nodes(n, ppn, pm, tmp_path):
     binomial over the leaders) for a commutative op, the flat binomial for a non-commutative one;
     MPI_Reduce_scatter: MPIR_Reduce_scatter_MV2's flat selection (non_comm forms included).  Above
     the programs' limit (8 ranks; 4 in the 8x1 and 6x2 cases) the host evaluates the message
-    schedules themselves (user_coll.cpp BigEval: recursive doubling, the ring's own chunk, the
+    schedules themselves (host_sched.cpp BigEval: recursive doubling, the ring's own chunk, the
     binomial; leaders' steps over more nodes than the limit; reduce-scatter's basic / recursive
     halving / ring for this rank's block, and the non-commutative reduce-scatter's recursive
     doubling as an expression tree)."""
@@ -514,7 +529,7 @@ def test_user_ops_across_nodes(n, ppn, pm, tmp_path):
                           "type": "MPI_INT", "seed": seed, "root": root})
             seed += 1
         # above the limit: basic (a 24-byte operand, half the blocks empty), halving, ring; the
-        # non_comm recursive doubling from its expression tree (user_coll.cpp BigEval::expr)
+        # non_comm recursive doubling from its expression tree (host_sched.cpp BigEval::expr)
         for per in (3, 400) if n <= pm else (0, 400, 12000) if commute else (5, 300):
             counts = [per] * n if not commute else [per + (r % 2) for r in range(n)]
             cases.append({"id": f"us{seed}", "kind": "user_reduce_scatter", "commute": commute, "count": sum(counts),
@@ -537,17 +552,76 @@ def test_user_ops_across_nodes(n, ppn, pm, tmp_path):
             counts = case["recvcounts"]
             total = sum(counts)
             xs = [((np.arange(total) + r) % 7).astype(np.int32) for r in range(n)]
-            if commute and rs_algo(n, total * 4) == "rs_basic":  # the multi-node reduce to 0 + scatter
-                parts = [ref_user.reduce(xs[j * ppn:(j + 1) * ppn], _ufn, True, TYPES["MPI_INT"][0], total, 0)
-                         for j in range(n // ppn)] if ppn > 1 else xs
-                full = ref_user.binomial(parts, _ufn, 0, True)
-                offs = np.cumsum([0] + counts)
-                want = [full[offs[r]:offs[r + 1]] for r in range(n)]
-            else:
-                want = ref_user.reduce_scatter(xs, _ufn, TYPES["MPI_INT"][0], counts, algo=rs_algo(n, total * 4)) \
-                    if commute else ref_user.reduce_scatter_noncomm(xs, _ufn, counts)
+            want = user_reduce_scatter_across(xs, commute, counts, ppn)
             for r in range(n):
                 assert np.array_equal(res(cid, r).view(np.int32), want[r]), (cid, r)
+
+
+# Every rank's calls of the user function across nodes, recorded as tests/test_gpu_collectives_mp.py
+# TRACES were: {(ranks, ranks per node, MV2AMD_MN_PROG_MAX): {case: [rank 0's calls, rank 1's, ...]}}
+TRACES_MN = {
+    (4, 2, 8): {
+        'ar': [[7, 7, 7], [7, 7, 7], [7, 7, 7], [7, 7, 7]],
+        'arn': [[2, 2, 2], [2, 2, 2], [2, 2, 2], [1, 1, 1]],
+        'ari': [[7, 7, 7], [7, 7, 7], [7, 7, 7], [7, 7, 7]],
+        'rc': [[], [7, 7, 7], [], []],
+        'rn': [[2, 2, 2], [2, 2, 2], [2, 2, 2], [1, 1, 1]],
+        'rsc': [[6, 6, 6], [], [6, 6, 6], [6, 6, 6]],
+        'rsn': [[2, 2, 2], [], [3, 3, 3], [1, 1, 1]],
+    },
+    (6, 2, 4): {
+        'ar': [[7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7]],
+        'arn': [[7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7]],
+        'ari': [[7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7], [7, 7, 7, 7, 7]],
+        'rc': [[], [7, 7, 7, 7, 7], [], [], [], []],
+        'rn': [[], [7, 7, 7, 7, 7], [], [], [], []],
+        'rsc': [[9, 9, 9, 9, 9], [], [9, 9, 9, 9, 9], [9, 9, 9, 9, 9], [9, 9, 9, 9, 9], [9, 9, 9, 9, 9]],
+        'rsn': [[2, 2, 2, 2, 2], [], [3, 3, 3, 3, 3], [1, 1, 1, 1, 1], [2, 2, 2, 2, 2], [1, 1, 1, 1, 1]],
+    },
+    (8, 1, 4): {
+        'ar': [[7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7],
+               [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7]],
+        'arn': [[7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7],
+                [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7]],
+        'ari': [[7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7],
+                [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7], [7, 7, 7, 7, 7, 7, 7]],
+        'rc': [[], [7, 7, 7, 7, 7, 7, 7], [], [], [], [], [], []],
+        'rn': [[], [7, 7, 7, 7, 7, 7, 7], [], [], [], [], [], []],
+        'rsc': [[11, 11, 11, 11, 11, 11, 11], [], [11, 11, 11, 11, 11, 11, 11], [11, 11, 11, 11, 11, 11, 11],
+                [11, 11, 11, 11, 11, 11, 11], [11, 11, 11, 11, 11, 11, 11], [], [11, 11, 11, 11, 11, 11, 11]],
+        'rsn': [[2, 2, 2, 2, 2, 2, 2], [], [3, 3, 3, 3, 3, 3, 3], [1, 1, 1, 1, 1, 1, 1], [2, 2, 2, 2, 2, 2, 2],
+                [1, 1, 1, 1, 1, 1, 1], [], [2, 2, 2, 2, 2, 2, 2]],
+    },
+}
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("n,ppn,pm", [(4, 2, 8), (6, 2, 4), (8, 1, 4)])
+def test_user_op_call_trace_across_nodes(n, ppn, pm, tmp_path):
+    """test_user_op_call_trace_is_unchanged across nodes, 7 MPI_INT elements: the two-level schedule
+    and a flat split at 4 ranks on 2 nodes; above the programs' limit (6 ranks on 3 nodes, limit 4)
+    the flat message schedules, the leaders' programs over the nodes' partials and Reduce_scatter's
+    block schedules; 8 nodes of one rank under a limit of 4: the leaders' message schedule over the
+    partials.  Every rank's trace of the user function's calls equals the recorded one exactly."""
+    rows = [("ar", "allreduce", 1, 0, 7), ("arn", "allreduce", 0, 0, 7), ("ari", "allreduce_inplace", 1, 0, 7),
+            ("rc", "reduce", 1, 0, 7), ("rn", "reduce", 0, 0, 7),
+            ("rsc", "reduce_scatter", 1, 0, None), ("rsn", "reduce_scatter", 0, 0, None)]
+    cases = trace_cases(n, rows)
+    res = run_workers(n, cases, tmp_path, ppn=ppn, extra_env={"MV2AMD_MN_PROG_MAX": str(pm)})
+    got = {case["id"]: [res(case["id"] + "_trace", r).tolist() for r in range(n)] for case in cases}
+    for case in cases:
+        coll, commute = case["coll"], bool(case["commute"])
+        xs = [x.ravel() for x in trace_operands(case, n)]
+        if coll in ("allreduce", "allreduce_inplace"):
+            want = user_allreduce_across(xs, commute, case["count"], ppn)
+        elif coll == "reduce":
+            full = user_reduce_across(xs, commute, case["count"], ppn, case["root"])
+            want = [full if r == case["root"] else None for r in range(n)]
+        else:
+            want = user_reduce_scatter_across(xs, commute, case["recvcounts"], ppn)
+        check_trace_results(case, n, res, want)
+    for case in cases:
+        assert got[case["id"]] == TRACES_MN[(n, ppn, pm)][case["id"]], (case["id"], got[case["id"]])
 
 
 @pytest.mark.timeout(300)

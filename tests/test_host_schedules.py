@@ -1,4 +1,4 @@
-"""CPU: the message schedules the host evaluates for a user op above 8 ranks (mpi/user_coll.cpp
+"""CPU: the message schedules the host evaluates for a user op above 8 ranks (mpi/host_sched.cpp
 BigEval, through the mv2h_host_sched_eval hook) against tests/ref_user.py's rank-by-rank
 restatements, with a function that is neither commutative nor associative (inout = 2 in + 3 inout)
 so that every operand order and bracketing shows.  ref_user's pt2pt_rs form (redscat_gather with

@@ -1,4 +1,4 @@
-"""CPU: the closed forms the host evaluator uses above 8 ranks (mpi/user_coll.cpp BigEval) against
+"""CPU: the closed forms the host evaluator uses above 8 ranks (mpi/host_sched.cpp BigEval) against
 the oracle's step-by-step simulations of the reference's schedules, at 9-16 ranks, on operands
 made of signed zeros, ±1 and NaN payloads so that MAX exposes every operand order:
 
